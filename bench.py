@@ -15,6 +15,9 @@ Extra keys on the same JSON line: encode / decode rows/s (same resident rows), t
 batching regime (batch_size 512, sequential steps, latency-bound), `roofline` for the dominant kernel
 (HIP events on the launch stream, inside the timed region) and `cpu_baseline` (the plain-PyTorch fp64
 restatement of the reference loops, timed on this box's host cores; N == 1 only).
+
+--dump-outputs DIR writes what the last timed step returned (parameters, [grads | loss], Adam moments) as
+DIR/<name>.npy; the same arguments give the same inputs, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -88,7 +91,14 @@ def parse():
     ap.add_argument("--pcie-rows", type=int, default=10_000_000, help="rows of the file of the PCIe-inclusive compress / decompress leg")
     ap.add_argument("--c3", action="store_true", help="also run the BASELINE configs[2] leg at --gpus 1 (one 12.5 M-row shard)")
     ap.add_argument("--c3-rows", type=int, default=0, help="rows per GPU of the configs[2] leg (default 100 M / n_gpus, at most 25 M)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed train step returned (parameters, gradients, loss, Adam moments) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 def log(msg):
@@ -126,6 +136,15 @@ def source_hash():
     for f in sorted(glob.glob(os.path.join(REPO, "baler_amd", "csrc", "*.h*"))):
         h.update(open(f, "rb").read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every (name, tensor): float64 stays float64, everything else is written as float32."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        np.save(os.path.join(path, name + ".npy"), (t if t.dtype == torch.float64 else t.float()).numpy())
+    log(f"outputs of the last timed step -> {path}: " + ", ".join(f"{k}{tuple(v.shape)}" for k, v in arrays.items()))
 
 
 def timed(fn, steps, world, dev):
@@ -372,6 +391,12 @@ def main():
     k_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev]))
     log(f"train: {value:.4g} rows/s, {1e3 * dt / a.steps:.3f} ms/step, fwd_bwd {k_ms:.3f} ms")
     final_loss = float(grads[-1].item())
+    if a.dump_outputs and rank == 0:
+        # before the side measurements below reuse flat / grads / m / v: what a caller of the K-th timed step holds.  The inputs
+        # are fixed by the arguments (counter-based rows, seeded init); the replicas are identical, so rank 0 speaks for all
+        npar = model.nparams
+        dump_outputs(a.dump_outputs, {"params": flat[:npar], "grads": grads[:npar], "loss": grads[-1:],
+                                      "adam_m": m[:npar], "adam_v": v[:npar]})
     wsum = torch.arange(1, flat.numel() + 1, dtype=torch.float64, device=dev)
     param_checksum = [float(flat.double().sum().item()), float((flat.double() * wsum).sum().item())]
     grad_checksum = [float(grads.double().sum().item()), float((grads.double() * wsum).sum().item())]

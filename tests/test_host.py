@@ -297,3 +297,18 @@ def test_npz_array_shape_reads_header_only(tmp_path):
     np.savez_compressed(tmp_path / "b.npz", data=a[0], names=np.array(["x"]))
     assert helper.npz_array_shape(str(tmp_path / "a.npz"), "data") == (2, 3, 4)
     assert helper.npz_array_shape(str(tmp_path / "b.npz"), "data") == (3, 4)
+
+
+def test_bench_dump_outputs_and_step_count_arguments(tmp_path):
+    """bench.py --dump-outputs writes float32 / float64 .npy files; --steps must name at least one timed step (rejected before any
+    GPU work)."""
+    sys.path.insert(0, REPO)
+    import bench
+    arrays = {"params": torch.arange(5, dtype=torch.float32), "grads": torch.ones(3, dtype=torch.float64),
+              "half": torch.ones(2, dtype=torch.bfloat16)}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    for name, dtype in (("params", np.float32), ("grads", np.float64), ("half", np.float32)):
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == dtype and np.array_equal(got, arrays[name].double().numpy())
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
