@@ -69,8 +69,13 @@ int bamd_device_count(void) {
 }
 
 int bamd_create(const int *dims, int n_layers, int mode, int device, bamd_handle **out) {
+    return bamd_create_act(dims, n_layers, BAMD_ACT_LEAKY_RELU, mode, device, out);
+}
+
+int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device, bamd_handle **out) {
     BAMD_REQUIRE(dims && out, "null argument");
     BAMD_REQUIRE(n_layers >= 2 && n_layers % 2 == 0, "n_layers must be even and >= 2");
+    BAMD_REQUIRE(act == BAMD_ACT_LEAKY_RELU || act == BAMD_ACT_RELU, "unknown activation");
     BAMD_REQUIRE(mode == BAMD_MODE_F32 || mode == BAMD_MODE_F64 || mode == BAMD_MODE_BF16, "unknown mode");
     for (int l = 0; l <= n_layers; ++l) BAMD_REQUIRE(dims[l] > 0, "layer widths must be positive");
     int ndev = bamd_device_count();
@@ -89,6 +94,7 @@ int bamd_create(const int *dims, int n_layers, int mode, int device, bamd_handle
     }
     bamd_handle *h = new bamd_handle();
     h->L = n_layers;
+    h->act = act;
     h->mode = mode;
     h->device = device;
     h->dims.assign(dims, dims + n_layers + 1);
@@ -117,6 +123,8 @@ int bamd_create(const int *dims, int n_layers, int mode, int device, bamd_handle
     if (rc) { bamd_destroy(h); return rc; }
     rc = fused64_setup(h);
     if (rc) { bamd_destroy(h); return rc; }
+    rc = fpga_setup(h);
+    if (rc) { bamd_destroy(h); return rc; }
     if (h->mode == BAMD_MODE_BF16 && !fused_serves_bf16_inference(h)) {   // (wide models in the bf16 mode are served by fused.hip)
         rc = bf16_setup(h);
         if (rc) { bamd_destroy(h); return rc; }
@@ -132,7 +140,7 @@ int bamd_create(const int *dims, int n_layers, int mode, int device, bamd_handle
             for (int l = 0; l <= n_layers; ++l) d += (l ? "-" : "") + std::to_string(dims[l]);
             fprintf(stderr, "[baler_amd] model %s: BAMD_MODE_BF16 has kernels for the 24-column AE and the 2500-25 / 625-7 / 512-6 wide models only; "
                             "this handle computes in float32 (%s)\n", d.c_str(),
-                    path == BAMD_PATH_GENERIC ? "layer-wise kernels" : "fused run-time-width kernels");
+                    path == BAMD_PATH_GENERIC ? "layer-wise kernels" : h->fpga_state ? "fused FPGA_prototype_model kernels" : "fused run-time-width kernels");
         }
     }
     if (path == BAMD_PATH_GENERIC || path == BAMD_PATH_FUSED_INFER) {
@@ -153,6 +161,7 @@ int bamd_create(const int *dims, int n_layers, int mode, int device, bamd_handle
 
 int bamd_path_of(const bamd_handle *h) {
     BAMD_REQUIRE(h, "null handle");
+    if (h->fpga_state) return BAMD_PATH_FUSED;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return BAMD_PATH_BF16;
     if (h->mode == BAMD_MODE_F64) return h->fused64_state ? BAMD_PATH_FUSED : BAMD_PATH_GENERIC;
     if (!h->fused_ok) return BAMD_PATH_GENERIC;
@@ -164,6 +173,7 @@ void bamd_destroy(bamd_handle *h) {
     DeviceGuard guard(h->device);
     fused_teardown(h);
     fused64_teardown(h);
+    fpga_teardown(h);
     bf16_teardown(h);
     bf16_train_teardown(h);
     comm_teardown(h);
@@ -178,6 +188,7 @@ void bamd_destroy(bamd_handle *h) {
 
 int64_t bamd_param_count(const bamd_handle *h) { return h ? h->nparams : 0; }
 int bamd_mode_of(const bamd_handle *h) { return h ? h->mode : BAMD_ERR_INVALID; }
+int bamd_act_of(const bamd_handle *h) { return h ? h->act : BAMD_ERR_INVALID; }
 
 int bamd_load_params(bamd_handle *h, const void *params, int dtype, void *stream) {
     BAMD_REQUIRE(h && params, "null argument");
@@ -265,6 +276,7 @@ int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, cons
     hipStream_t s = (hipStream_t)stream;
     if (int rc = bf16_sync(h, s)) return rc;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return bf16_encode(h, x, x_dtype, n_rows, features, z, z_dtype, s);
+    if (h->fpga_state) return fpga_infer(h, 0, x, x_dtype, n_rows, features, z, z_dtype, nullptr, nullptr, nullptr, s);
     if (h->fused_ok) return fused_encode(h, x, x_dtype, n_rows, features, z, z_dtype, s);
     if (h->mode == BAMD_MODE_F64) {
         const int rc = fused64_infer(h, 0, x, x_dtype, n_rows, features, z, z_dtype, nullptr, nullptr, nullptr, s);
@@ -281,6 +293,7 @@ int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, cons
     hipStream_t s = (hipStream_t)stream;
     if (int rc = bf16_sync(h, s)) return rc;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return bf16_decode(h, z, z_dtype, n_rows, features, int_mask, out, out_dtype, s);
+    if (h->fpga_state) return fpga_infer(h, 1, z, z_dtype, n_rows, nullptr, out, out_dtype, features, int_mask, nullptr, s);
     if (h->fused_ok) return fused_decode(h, z, z_dtype, n_rows, features, int_mask, out, out_dtype, s);
     if (h->mode == BAMD_MODE_F64 && (!features || out_dtype == BAMD_F64)) {      // (un-normalised output is float64, as renormalize_k's)
         const int rc = fused64_infer(h, 1, z, z_dtype, n_rows, nullptr, out, out_dtype, features, int_mask, nullptr, s);
@@ -296,6 +309,7 @@ int bamd_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows
     hipStream_t s = (hipStream_t)stream;
     if (int rc = bf16_sync(h, s)) return rc;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return bf16_forward_loss(h, x, x_dtype, n_rows, features, recon, recon_dtype, loss_sum, s);
+    if (h->fpga_state) return fpga_infer(h, 2, x, x_dtype, n_rows, features, recon, recon_dtype, nullptr, nullptr, loss_sum, s);
     if (h->fused_ok) return fused_forward_loss(h, x, x_dtype, n_rows, features, recon, recon_dtype, loss_sum, s);
     if (h->mode == BAMD_MODE_F64) {
         const int rc = fused64_infer(h, 2, x, x_dtype, n_rows, features, recon, recon_dtype, nullptr, nullptr, loss_sum, s);
@@ -317,6 +331,7 @@ int bamd_fwd_bwd(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, con
         if (int rc = bf16_train_sync(h, s)) return rc;
         return bf16_fwd_bwd(h, x, x_dtype, n_rows, features, grads, s);
     }
+    if (fpga_trains(h, n_rows)) return fpga_step(h, x, x_dtype, n_rows, features, nullptr, grads, nullptr, nullptr, nullptr, nullptr, nullptr, s);
     if (h->fused_ok) return fused_fwd_bwd(h, x, x_dtype, n_rows, features, grads, s);
     if (h->mode == BAMD_MODE_F64) {   // small batches: fp64 chain + weight-gradient tiles; otherwise the layer-wise kernels
         int rc = fused64_step(h, x, x_dtype, n_rows, features, grads, nullptr, nullptr, nullptr, nullptr, nullptr, s);
@@ -330,6 +345,8 @@ int bamd_fwd_bwd_latent(bamd_handle *h, const void *x, int x_dtype, int64_t n_ro
     BAMD_CHECK_MODEL(h);
     BAMD_REQUIRE(grads && x && n_rows > 0, "bad arguments");
     if (!latent_grad) return bamd_fwd_bwd(h, x, x_dtype, n_rows, features, grads, stream);
+    if (fpga_trains(h, n_rows))
+        return fpga_step(h, x, x_dtype, n_rows, features, latent_grad, grads, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
     // the regulariser's gradient enters between the decoder's and the encoder's backward products: layer-wise path
     return generic_fwd_bwd(h, x, x_dtype, n_rows, features, grads, (hipStream_t)stream, latent_grad);
 }
@@ -372,6 +389,8 @@ int bamd_train_step(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, 
         if (rc) return rc;
         return bamd_adam_step(h, params, grads, m, v, hp, loss_accum, stream);
     }
+    if (n_rows > 0 && fpga_trains(h, n_rows))      // forward + backward, then the slab sum with Adam: two launches
+        return fpga_step(h, x, x_dtype, n_rows, features, nullptr, grads, params, m, v, hp, loss_accum, s);
     if (n_rows > 0 && !bf16_kernels_train(h, n_rows)) {
         int rc = fused_train_step(h, x, x_dtype, n_rows, features, grads, params, m, v, *hp, loss_accum, s);
         if (rc != BAMD_ERR_UNSUPPORTED) {

@@ -55,6 +55,7 @@ struct DevBuf {
 struct bamd_handle {
     int L = 0;
     int mode = 0;
+    int act = BAMD_ACT_LEAKY_RELU;  // bamd_act: the activation after every layer but the last encoder and the last decoder layer
     int device = 0;
     std::vector<int> dims;          // L+1
     std::vector<int64_t> w_off;     // offset of W_l in the flat vector
@@ -83,8 +84,10 @@ struct bamd_handle {
     void *comm = nullptr;           // ncclComm_t of data-parallel training (comm.hip); null: single process
     bool comm_owned = false;        // created by bamd_comm_init (destroyed with the handle) vs attached by the caller
     int comm_world = 0;
+    void *fpga_state = nullptr;     // FPGA_prototype_model shapes with ReLU (fpga.hip)
 
     bool has_act(int l) const { return !(l == L / 2 - 1 || l == L - 1); }
+    bool leaky() const { return act == BAMD_ACT_LEAKY_RELU; }   // the fused / fp64 / bf16 families implement LeakyReLU(0.01) only
 };
 
 namespace bamd {
@@ -129,6 +132,17 @@ int generic_small_train_step(bamd_handle *h, const void *x, int x_dtype, int64_t
 int generic_activation_means(bamd_handle *h, const void *x, int x_dtype, int64_t n,
                              const double *features, double *out, int max_nodes, hipStream_t s);
 
+// ---- fpga.hip (FPGA_prototype_model [n, 20, 10, z, 10, 20, n] with ReLU, n <= 64, z <= 32; F32 / F64) ----------------------
+bool fpga_matches(const bamd_handle *h);         // the shape and activation of the family (whatever the mode)
+int fpga_setup(bamd_handle *h);                  // leaves h->fpga_state null for other shapes / modes or BALER_AMD_FORCE_GENERIC=1
+void fpga_teardown(bamd_handle *h);
+// kind: 0 = encode, 1 = decode (renorm / int_mask: un-normalise into a float64 output), 2 = forward + loss
+int fpga_infer(bamd_handle *h, int kind, const void *in, int in_dtype, int64_t n, const double *features, void *out, int out_dtype,
+               const double *renorm, const uint8_t *int_mask, double *loss_sum, hipStream_t s);
+bool fpga_trains(const bamd_handle *h, int64_t n_rows);   // this training batch runs on fpga.hip (else: the layer-wise kernels)
+// fwd + loss + bwd (hp == nullptr), or the whole training step with Adam in the second launch; latent_grad may be null
+int fpga_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, const void *latent_grad, void *grads,
+              void *params, void *m, void *v, const bamd_adam *hp, double *loss_accum, hipStream_t s);
 
 // Sum of n doubles by ONE 256-thread workgroup in a fixed order (bitwise reproducible): 256 strided partial sums, then a fixed
 // tree through `sh` (256 doubles of LDS).  The result is valid in thread 0.  (A single thread adding the partials one after the

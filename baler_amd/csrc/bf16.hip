@@ -582,10 +582,10 @@ const Bf16Ops *find_bf16(const bamd_handle *h) {
 
 }  // namespace
 
-bool bf16_has_kernels(const bamd_handle *h) { return find_bf16(h) != nullptr; }
+bool bf16_has_kernels(const bamd_handle *h) { return h->leaky() && find_bf16(h) != nullptr; }
 
 int bf16_setup(bamd_handle *h) {
-    const Bf16Ops *ops = find_bf16(h);
+    const Bf16Ops *ops = h->leaky() ? find_bf16(h) : nullptr;
     if (!ops) {
         set_error("BAMD_MODE_BF16 is instantiated for the 24-column AE (latent 15/12/8/6) and the wide models (2500-25, 512-6) only; use BAMD_MODE_F32");
         return BAMD_ERR_UNSUPPORTED;

@@ -1103,7 +1103,7 @@ extern "C" int bamd_debug_bf16_trace(unsigned long long *out) {
 #endif
 
 int bf16_train_setup(bamd_handle *h) {
-    const TrainOps *ops = find_train(h);
+    const TrainOps *ops = h->leaky() ? find_train(h) : nullptr;
     if (!ops) return BAMD_OK;                  // no bf16 training kernels for this shape: training calls use the fp32 layer-wise path
     const char *env = getenv("BALER_AMD_BF16_TRAIN");
     if (env && env[0] == '0') return BAMD_OK;

@@ -4659,6 +4659,7 @@ static void state_env(FusedState *st) {
 }
 int fused_setup(bamd_handle *h) {
     h->fused_ok = false;
+    if (!h->leaky()) return BAMD_OK;          // every kernel here computes LeakyReLU(0.01)
     const FusedOps *ops = find_ops(h);
     if (!ops) return BAMD_OK;
     const char *env = getenv("BALER_AMD_FORCE_GENERIC");
@@ -4756,10 +4757,10 @@ int64_t fused_latency_rows(const bamd_handle *h) {   // the handle's small-batch
     return h->fused_ok ? ((const FusedState *)h->fused_state)->latency_max_rows : 0;
 }
 bool fused_has_bf16_kernels(const bamd_handle *h) {
-    return ImplWide<2500, 25>::matches(h) || ImplWide<625, 7>::matches(h) || ImplWide<512, 6>::matches(h);
+    return h->leaky() && (ImplWide<2500, 25>::matches(h) || ImplWide<625, 7>::matches(h) || ImplWide<512, 6>::matches(h));
 }
 bool fused_serves_bf16_inference(const bamd_handle *h) {   // wide models in the bf16 mode: encode / decode live in fused.hip
-    return h->fused_ok && ((const FusedState *)h->fused_state)->ops->pack_extra != nullptr;
+    return h->leaky() && h->fused_ok && ((const FusedState *)h->fused_state)->ops->pack_extra != nullptr;
 }
 
 void fused_params_changed(bamd_handle *h) {   // after an optimiser step: further packed copies are refreshed on demand

@@ -1065,6 +1065,7 @@ const Ops64 *find64(const bamd_handle *h) {
 }  // namespace
 
 int fused64_setup(bamd_handle *h) {
+    if (!h->leaky()) return BAMD_OK;          // LeakyReLU(0.01) chains only
     const Ops64 *ops = find64(h);
     if (!ops) return BAMD_OK;
     const char *env = getenv("BALER_AMD_FORCE_GENERIC");

@@ -46,14 +46,20 @@ template <typename T> struct Opnd {
 };
 
 enum { EPI_FWD = 0, EPI_DX = 1, EPI_DW = 2, EPI_FWD_LOSS = 3 };   // FWD_LOSS: last layer of a training step: writes dL/drecon, sums the loss
+enum { EPI_ACT_NONE = 0, EPI_ACT_LEAKY = 1, EPI_ACT_RELU = 2 };
+
+// torch.relu (relu(nan) = nan, relu(-inf) = 0) and threshold_backward (the gradient passes where the output is > 0)
+template <typename T> __device__ __forceinline__ T relu_fwd(T v) { return (v > (T)0 || v != v) ? v : (T)0; }
+template <typename T> __device__ __forceinline__ T relu_bwd(T y, T g) { return y <= (T)0 ? (T)0 : g; }
 
 template <typename T> struct Epi {
     T *out;            // FWD/DX: output matrix
     int64_t ld;        // its leading dimension
     int64_t n_rows, n_cols;
     const T *bias;     // FWD
-    int act;           // FWD: apply leaky relu
+    int act;           // FWD: EPI_ACT_NONE / EPI_ACT_LEAKY / EPI_ACT_RELU
     const T *ymask;    // DX: post-activation output of the previous layer (sign = pre-activation sign)
+    int mask_act;      // DX: the activation ymask went through (EPI_ACT_LEAKY / EPI_ACT_RELU)
     int64_t ld_mask;
     const T *add;      // DX: extra gradient added to the result (latent regulariser injected at the bottleneck)
     int64_t ld_add;
@@ -72,7 +78,8 @@ __device__ __forceinline__ void epilogue(const Epi<T> &e, int64_t row, int64_t c
         // utils.py:195-199 fused into de4's store: out = dL/drecon = 2 (r - x) / C, loss partial += (r - x)^2
         if (row < e.n_rows && col < e.n_cols) {
             val += e.bias[col];
-            if (e.act) val = val > (T)0 ? val : val * (T)kSlope;
+            if (e.act == EPI_ACT_LEAKY) val = val > (T)0 ? val : val * (T)kSlope;
+            else if (e.act == EPI_ACT_RELU) val = relu_fwd(val);
             const T d = val - e.xref[row * e.ld + col];
             lsum += (double)d * (double)d;
             e.out[row * e.ld + col] = (T)(e.grad_scale * (double)d);
@@ -80,12 +87,16 @@ __device__ __forceinline__ void epilogue(const Epi<T> &e, int64_t row, int64_t c
     } else if (EPI == EPI_FWD) {
         if (row < e.n_rows && col < e.n_cols) {
             val += e.bias[col];
-            if (e.act) val = val > (T)0 ? val : val * (T)kSlope;
+            if (e.act == EPI_ACT_LEAKY) val = val > (T)0 ? val : val * (T)kSlope;
+            else if (e.act == EPI_ACT_RELU) val = relu_fwd(val);
             e.out[row * e.ld + col] = val;
         }
     } else if (EPI == EPI_DX) {
         if (row < e.n_rows && col < e.n_cols) {
-            if (e.ymask) val = e.ymask[row * e.ld_mask + col] > (T)0 ? val : val * (T)kSlope;
+            if (e.ymask) {
+                const T y = e.ymask[row * e.ld_mask + col];
+                val = e.mask_act == EPI_ACT_RELU ? relu_bwd(y, val) : (y > (T)0 ? val : val * (T)kSlope);
+            }
             if (e.add) val += e.add[row * e.ld_add + col];
             e.out[row * e.ld + col] = val;
         }
@@ -1148,6 +1159,8 @@ static int stage_input(bamd_handle *h, const void *x, int x_dtype, int64_t row0,
     return launch_convert(src, x_dtype, dst, td, rows * width, s);
 }
 
+static int epi_act(const bamd_handle *h) { return h->act == BAMD_ACT_RELU ? EPI_ACT_RELU : EPI_ACT_LEAKY; }
+
 template <typename T>
 static void launch_fwd_layer(bamd_handle *h, int l, const T *xin, T *yout, int64_t rows, hipStream_t s) {
     const T *P = (const T *)h->params.p;
@@ -1156,7 +1169,7 @@ static void launch_fwd_layer(bamd_handle *h, int l, const T *xin, T *yout, int64
     Opnd<T> B{P + h->w_off[l], K, 1, N, -1};
     Epi<T> e{};
     e.out = yout; e.ld = N; e.n_rows = rows; e.n_cols = N;
-    e.bias = P + h->b_off[l]; e.act = h->has_act(l) ? 1 : 0;
+    e.bias = P + h->b_off[l]; e.act = h->has_act(l) ? epi_act(h) : EPI_ACT_NONE;
     launch_gemm<T, EPI_FWD, true, true>(A, B, (int64_t)K, e, rows, N, 1, s);
 }
 
@@ -1540,7 +1553,7 @@ static int fwd_bwd_T(bamd_handle *h, const void *x, int x_dtype, int64_t n, cons
                 Opnd<T> B{P + h->w_off[l], K, 1, N, -1};
                 Epi<T> e{};
                 e.out = wk.dz[l]; e.ld = N; e.n_rows = rows; e.n_cols = N;
-                e.bias = P + h->b_off[l]; e.act = h->has_act(l) ? 1 : 0;
+                e.bias = P + h->b_off[l]; e.act = h->has_act(l) ? epi_act(h) : EPI_ACT_NONE;
                 e.xref = x0; e.loss_part = (double *)h->lossp.p; e.grad_scale = 2.0 / c;
                 launch_gemm<T, EPI_FWD_LOSS, true, true>(A, B, (int64_t)K, e, rows, N, 1, s);
             }
@@ -1581,7 +1594,7 @@ static int fwd_bwd_T(bamd_handle *h, const void *x, int x_dtype, int64_t n, cons
                 Opnd<T> B{P + h->w_off[l], 1, K, K, -1};
                 Epi<T> e{};
                 e.out = wk.dz[l - 1]; e.ld = K; e.n_rows = rows; e.n_cols = K;
-                e.ymask = h->has_act(l - 1) ? wk.y[l] : nullptr; e.ld_mask = K;
+                e.ymask = h->has_act(l - 1) ? wk.y[l] : nullptr; e.ld_mask = K; e.mask_act = epi_act(h);
                 if (latent_grad && l == h->L / 2) { e.add = (const T *)latent_grad + r0 * K; e.ld_add = K; }   // dL/dz of the caller's regulariser
                 launch_gemm<T, EPI_DX, true, false>(A, B, (int64_t)N, e, rows, K, 1, s);
             }
@@ -1672,6 +1685,10 @@ static int act_means_T(bamd_handle *h, const void *x, int x_dtype, int64_t n, co
 
 int generic_activation_means(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features,
                              double *out, int max_nodes, hipStream_t s) {
+    if (!h->leaky()) {      // leaky_relu means are what the reference's hooks record (models.py:160-183); the ReLU model has no hooks
+        set_error("activation_means: implemented for LeakyReLU models only");
+        return BAMD_ERR_UNSUPPORTED;
+    }
     if (h->esize == 8) return act_means_T<double>(h, x, x_dtype, n, features, out, max_nodes, s);
     return act_means_T<float>(h, x, x_dtype, n, features, out, max_nodes, s);
 }

@@ -4,6 +4,7 @@ Mirrors ``baler/modules/models.py`` for the two dense topologies on the hot path
 
 * ``AE``            (reference models.py:116-183) -- fp64 state dict, 24->200->100->50->z->...->24
 * ``CFD_dense_AE``  (reference models.py:186-253) -- fp32 state dict, same topology, wide ends
+* ``FPGA_prototype_model`` (reference models.py:410-463) -- fp64 state dict, n->20->10->z->10->20->n with ReLU
 
 Protocol kept: ctor ``(n_features, z_dim)``, ``encode / decode / forward``, ``state_dict`` /
 ``load_state_dict(strict=False)``, ``to``, ``train`` / ``eval``, ``children``, ``parameters``,
@@ -39,11 +40,19 @@ def ae_dims(n_features, z_dim):
     return [int(n_features), 200, 100, 50, int(z_dim), 50, 100, 200, int(n_features)]
 
 
-def tensor_layout(dims):
+def fpga_dims(n_features, z_dim):
+    """Layer widths of the reference's FPGA_prototype_model (models.py:414-424)."""
+    return [int(n_features), 20, 10, int(z_dim), 10, 20, int(n_features)]
+
+
+def tensor_layout(dims, names=None):
     """[(key, offset, shape)] of the flat parameter vector in state-dict order."""
     out, off = [], 0
     for l in range(len(dims) - 1):
-        name = _LAYER_NAMES[l] if len(dims) - 1 == 8 else f"fc{l + 1}"
+        if names is not None:
+            name = names[l]
+        else:
+            name = _LAYER_NAMES[l] if len(dims) - 1 == 8 else f"fc{l + 1}"
         shape = (dims[l + 1], dims[l])
         out.append((name + ".weight", off, shape))
         off += shape[0] * shape[1]
@@ -84,13 +93,16 @@ class _LayerView:
 
 class DenseAE:
     state_dtype = torch.float64
+    act = "leaky_relu"           # what follows every layer but the last encoder and the last decoder layer
+    layer_names = None           # state-dict prefixes (None: the 8-layer reference names)
+    make_dims = staticmethod(ae_dims)
 
     def __init__(self, n_features, z_dim, *args, mode=None, **kwargs):
         self.n_features = int(n_features)
         self.z_dim = int(z_dim)
-        self.dims = ae_dims(n_features, z_dim)
+        self.dims = self.make_dims(n_features, z_dim)
         self.mode = mode or _DEFAULT_MODE
-        self.layout, self.nparams = tensor_layout(self.dims)
+        self.layout, self.nparams = tensor_layout(self.dims, self.layer_names)
         self.param_dtype = torch.float64 if self.mode in ("fp64", "f64") else torch.float32
         # master parameters: flat, state-dict order, +1 slot so the vector can double as a
         # [params | scratch] buffer; created on CPU like the reference, moved by .to()
@@ -176,7 +188,7 @@ class DenseAE:
                 "call model.to('cuda:0') on a GPU box")
         if self._handle is None:
             with torch.cuda.device(self.flat.device):
-                self._handle = native.Handle(self.dims, self.mode, self.flat.device.index)
+                self._handle = native.Handle(self.dims, self.mode, self.flat.device.index, act=self.act)
             self._dirty = True
         if self._dirty:
             with torch.cuda.device(self.flat.device):
@@ -248,3 +260,20 @@ class AE(DenseAE):
 class CFD_dense_AE(DenseAE):
     """reference models.CFD_dense_AE (models.py:186-253): float32 checkpoint."""
     state_dtype = torch.float32
+
+
+class FPGA_prototype_model(DenseAE):
+    """reference models.FPGA_prototype_model (models.py:410-463): float64 checkpoint, en1 en2 en3 de1 de2 de3 with ReLU after
+    en1, en2, de1 and de2 -- the model helper.perform_hls4ml_conversion (helper.py:746-800) expects.  Like the reference it has no
+    activation hooks: training with config.activation_extraction raises (training.py:287)."""
+    state_dtype = torch.float64
+    act = "relu"
+    layer_names = ("en1", "en2", "en3", "de1", "de2", "de3")
+    make_dims = staticmethod(fpga_dims)
+    supports_activation_extraction = False
+
+    def store_hooks(self):
+        raise NotImplementedError("FPGA_prototype_model has no activation hooks (reference models.py:410-463; training.py:287)")
+
+    def capture_activations(self, x, features=None):
+        raise NotImplementedError("FPGA_prototype_model has no activation hooks (reference models.py:410-463; training.py:287)")

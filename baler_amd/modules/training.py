@@ -234,6 +234,9 @@ def train(model, variables, train_data, test_data, project_path, config):
     """reference training.py:150-348 (same artefacts: loss_data.npy, activations.npy, model_{epoch}.pt).
     ``train_data`` / ``test_data``: arrays / device tensors (every rank holds them whole and slices its share of a
     batch) or ``ShardedRows`` from ``helper.process`` (every rank holds only its share)."""
+    if getattr(config, "activation_extraction", False) and not getattr(model, "supports_activation_extraction", True):
+        raise NotImplementedError(f"activation_extraction needs activation hooks, which {type(model).__name__} does not have "
+                                  "(the reference fails at model.store_hooks(), training.py:287)")
     if config.deterministic_algorithm:
         random.seed(0)
         torch.manual_seed(0)

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("BALER_AMD_LIB", os.path.join(_HERE, "libbaler_amd.so"
 F32, F64 = 0, 1
 MODE_F32, MODE_F64, MODE_BF16 = 0, 1, 2
 MODE_NAMES = {"fp32": MODE_F32, "f32": MODE_F32, "fp64": MODE_F64, "f64": MODE_F64, "bf16": MODE_BF16}
+ACT_LEAKY_RELU, ACT_RELU = 0, 1
+ACT_NAMES = {"leaky_relu": ACT_LEAKY_RELU, "relu": ACT_RELU}
 
 # every symbol include/baler_amd.h declares (tests check that the library exports all of them)
 SYMBOLS = (
@@ -25,7 +27,7 @@ SYMBOLS = (
     "bamd_adam_step", "bamd_train_step", "bamd_emd_rows", "bamd_activation_means",
     "bamd_error_deltas", "bamd_apply_deltas", "bamd_fwd_bwd_latent", "bamd_swd", "bamd_col_minmax", "bamd_path_of",
     "bamd_train_epoch", "bamd_comm_unique_id", "bamd_comm_init", "bamd_comm_attach", "bamd_comm_release", "bamd_comm_world",
-    "bamd_allreduce_sum", "bamd_train_epoch_dp",
+    "bamd_allreduce_sum", "bamd_train_epoch_dp", "bamd_create_act", "bamd_act_of",
 )
 
 
@@ -58,6 +60,9 @@ def lib():
     L.bamd_last_error.restype = ctypes.c_char_p
     L.bamd_device_count.restype = ci
     L.bamd_create.argtypes = [ctypes.POINTER(ci), ci, ci, ci, ctypes.POINTER(vp)]
+    L.bamd_create_act.argtypes = [ctypes.POINTER(ci), ci, ci, ci, ci, ctypes.POINTER(vp)]
+    L.bamd_act_of.argtypes = [vp]
+    L.bamd_act_of.restype = ci
     L.bamd_destroy.argtypes = [vp]
     L.bamd_destroy.restype = None
     L.bamd_param_count.argtypes = [vp]
@@ -255,20 +260,26 @@ def apply_deltas(out, rows, cols, deltas):
 class Handle:
     """Owns a bamd_handle*; parameters and optimiser state stay in caller-owned torch tensors."""
 
-    def __init__(self, dims, mode="fp32", device=None):
+    def __init__(self, dims, mode="fp32", device=None, act="leaky_relu"):
         require_gpu()
         self.dims = [int(d) for d in dims]
         self.mode = MODE_NAMES[mode] if isinstance(mode, str) else int(mode)
+        act_code = ACT_NAMES[act] if isinstance(act, str) else int(act)
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         arr = (ctypes.c_int * len(self.dims))(*self.dims)
         h = ctypes.c_void_p()
-        _check(lib().bamd_create(arr, len(self.dims) - 1, self.mode, self.device.index, ctypes.byref(h)),
-               "bamd_create")
+        _check(lib().bamd_create_act(arr, len(self.dims) - 1, act_code, self.mode, self.device.index, ctypes.byref(h)),
+               "bamd_create_act")
         self._h = h
         self.nparams = int(lib().bamd_param_count(h))
         self.param_dtype = torch.float64 if self.mode == MODE_F64 else torch.float32
         # the mode the library computes in: "bf16" asked of a shape without bf16 kernels is served in float32 (notice on stderr)
         self.compute_mode = int(lib().bamd_mode_of(h))
+
+    @property
+    def act(self):
+        """The activation the handle computes with: "leaky_relu" or "relu" (bamd_act_of)."""
+        return {ACT_LEAKY_RELU: "leaky_relu", ACT_RELU: "relu"}[int(lib().bamd_act_of(self._h))]
 
     def close(self):
         if getattr(self, "_h", None):

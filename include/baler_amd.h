@@ -93,6 +93,23 @@ int bamd_device_count(void);
 int bamd_create(const int *dims, int n_layers, int mode, int device, bamd_handle **out);
 void bamd_destroy(bamd_handle *h);
 
+/* activation that follows every layer except the last encoder layer and the last decoder layer */
+typedef enum bamd_act {
+    BAMD_ACT_LEAKY_RELU = 0,   /* F.leaky_relu(0.01): AE / CFD_dense_AE (models.py:141-152) */
+    BAMD_ACT_RELU = 1          /* nn.ReLU: FPGA_prototype_model (models.py:410-463) */
+} bamd_act;
+/* The create call above with the activation as an argument; the create call is exactly this one with BAMD_ACT_LEAKY_RELU.
+ * Replaces: models.FPGA_prototype_model.__init__ (models.py:410-427) and data_processing.initialise_model / load_model
+ * (data_processing.py:76-110) for that model, whose dims are (n_features, 20, 10, z, 10, 20, n_features) with ReLU after en1, en2,
+ * de1 and de2.  ReLU follows torch: relu(nan) = nan, relu(-inf) = 0, and the backward pass lets the gradient through where the
+ * layer's output is > 0 (threshold_backward; an exact-zero pre-activation gets a zero gradient).  A BAMD_ACT_RELU handle runs on the
+ * fused FPGA_prototype_model kernels (fpga.hip) for n_features <= 64 and z <= 32 in BAMD_MODE_F32 / BAMD_MODE_F64, and on the
+ * layer-wise kernels for every other shape; the LeakyReLU kernel families never serve it.  In BAMD_MODE_BF16 it is created as a
+ * float32 handle with a notice on stderr.  The activation-means diagnostic returns BAMD_ERR_UNSUPPORTED for it (the reference model
+ * has no activation hooks either, training.py:287). */
+int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device, bamd_handle **out);
+int bamd_act_of(const bamd_handle *h);     /* the handle's bamd_act, or BAMD_ERR_INVALID for a null handle */
+
 /* Which kernels serve this handle's throughput calls (bamd_encode / bamd_decode / bamd_fwd_bwd at large batches).  The fused
  * register-chained / wide-layer kernels are template instantiations.  EXACT instantiations for the shapes the reference ships configs
  * for: AE(24, z) for z in {15, 12, 10, 8, 6, 5, 4, 3, 2} (models.py:116-183 at the compression ratios of baler.py:117-123),
@@ -108,7 +125,11 @@ void bamd_destroy(bamd_handle *h);
  *   - 48 .. 4096 columns, latent <= 63, that no class above takes: the wide-layer kernels with the column count and the latent as
  *     kernel arguments -- encode / decode / forward + loss fused, a training pass = two fused row-local launches + the layer-wise
  *     weight-gradient kernels, as for the exact wide shapes (BAMD_PATH_FUSED; BALER_AMD_WIDE_CLASS=0 switches the class off);
- *   - F64 handles: class instantiations of the fp64 kernels for up to 63 columns with a latent of up to 31.
+ *   - F64 handles: class instantiations of the fp64 kernels for up to 63 columns with a latent of up to 31;
+ *   - BAMD_ACT_RELU handles of FPGA_prototype_model (n_features, 20, 10, z, 10, 20, n_features) for n_features <= 64 and z <= 32,
+ *     BAMD_MODE_F32 and BAMD_MODE_F64: fused kernels with n_features and z as kernel arguments (fpga.hip; BAMD_PATH_FUSED;
+ *     fp32 training batches above 8192 rows run on the layer-wise kernels, which are faster there).
+ *     Every other BAMD_ACT_RELU handle runs on the layer-wise kernels.
  * Any other shape (other hidden widths, more than 4096 columns, a latent above 63) runs on the layer-wise kernels (activations
  * through HBM, 1.5-2.5x slower): bamd_create prints one line to stderr for such a handle unless BALER_AMD_QUIET=1.  There is no model
  * object in the reference to query (models.py builds nn.Linear layers of any width); this call exists so that callers and tests can tell. */
