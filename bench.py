@@ -11,10 +11,17 @@ forward + sum-of-squares loss + backward over the rank's 1M rows, ONE RCCL sum-a
 [grads | loss] buffer (N > 1), one fused Adam step.  Weak scaling: rows per GPU fixed, global batch =
 N x 1M rows.  `value` = N * rows * K / time (max over ranks, barrier + synchronize on both sides).
 
-Extra keys on the same JSON line: encode / decode rows/s (same resident rows), the strict reference
-batching regime (batch_size 512, sequential steps, latency-bound), `roofline` for the dominant kernel
-(HIP events on the launch stream, inside the timed region) and `cpu_baseline` (the plain-PyTorch fp64
-restatement of the reference loops, timed on this box's host cores; N == 1 only).
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, the
+checksums of the last step and `roofline` for the dominant kernel (HIP events on the launch stream,
+inside the timed region, so it costs no run of its own).
+
+--full adds the side measurements, each a run of its own, to the same JSON line: encode / decode rows/s
+(same resident rows), bf16 and fp64 modes, the strict reference batching regime (batch_size 512,
+sequential steps, latency-bound), the other BASELINE configs, the PCIe-inclusive leg, the all-reduce
+and data-parallel step timings (N > 1 or a forced process group), the configs[2] leg (N > 1) and
+`cpu_baseline` (the plain-PyTorch fp64 restatement of the reference loops, timed on this box's host
+cores; N == 1 only).  --no-extras / --no-cpu-baseline drop parts of that; --c3 runs the configs[2]
+leg in any run.
 
 --dump-outputs DIR writes what the last timed step returned (parameters, [grads | loss], Adam moments) as
 DIR/<name>.npy; the same arguments give the same inputs, so two builds can be compared output for output.
@@ -85,11 +92,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rows", type=int, default=1_000_000, help="rows per GPU")
     ap.add_argument("--mode", default=os.environ.get("BALER_AMD_MODE", "fp32"), choices=["fp32", "fp64"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip encode/decode/small-batch/bf16/C4/C5 side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (extras, all-reduce, configs[2] leg at N > 1, CPU baseline); "
+                         "a plain run times the K steps and nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip encode/decode/small-batch/bf16/C4/C5 side measurements")
     ap.add_argument("--cpu-rows", type=int, default=1_000_000, help="rows of the CPU baseline's epoch (bounded to ~20 s)")
     ap.add_argument("--pcie-rows", type=int, default=10_000_000, help="rows of the file of the PCIe-inclusive compress / decompress leg")
-    ap.add_argument("--c3", action="store_true", help="also run the BASELINE configs[2] leg at --gpus 1 (one 12.5 M-row shard)")
+    ap.add_argument("--c3", action="store_true", help="also run the BASELINE configs[2] leg (at --gpus 1: one 12.5 M-row shard; "
+                                                      "--full runs it at N > 1 without being asked)")
     ap.add_argument("--c3-rows", type=int, default=0, help="rows per GPU of the configs[2] leg (default 100 M / n_gpus, at most 25 M)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed train step returned (parameters, gradients, loss, Adam moments) as DIR/<name>.npy")
@@ -336,9 +347,11 @@ def main():
 
     # The library's own RCCL communicator (bamd_comm_init: fwd_bwd -> ncclAllReduce -> Adam in ONE host call), built in a helper thread
     # with a deadline: should ncclCommInitRank not return on some node (it never failed on the boxes this was developed on), the run says
-    # so on the line and measures every data-parallel loop as three Python calls, as rounds 1-5 did.  `value` never depends on it.
+    # so on the line and measures every data-parallel loop as three Python calls, as rounds 1-5 did.  `value` never depends on it, and
+    # only the side measurements of --full use it, so a plain run does not build it.
     lib_dp, lib_dp_error = False, None
-    if coll and torch.distributed.get_backend() == "nccl" and os.environ.get("BALER_AMD_LIB_COMM", "1") != "0":
+    lib_comm = a.full and coll and torch.distributed.get_backend() == "nccl" and os.environ.get("BALER_AMD_LIB_COMM", "1") != "0"
+    if lib_comm:
         import threading
         att = {}
 
@@ -421,7 +434,7 @@ def main():
         "param_checksum": param_checksum, "grad_checksum": grad_checksum,   # after the K timed steps (float64 sums: bit-exact run to run)
         "source_hash": source_hash(),
     }
-    if coll:
+    if coll and a.full:
         # the 247 KB [grads | loss] all-reduce alone (latency-bound on xGMI), 200 back-to-back calls
         for _ in range(10):
             bdist.allreduce_sum(grads)
@@ -461,7 +474,7 @@ def main():
             "mix_replay_us_per_iteration": 54.0,
             "frac_at_mix_replay": (FLOP_TRAIN_ROW * a.rows / ((iters * 54.0 + 15.0) * 1e-6) / 1e12 / PEAK_TFLOPS["fp32"]) if iters >= 1 else None})
 
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         extra_roof = {}
         # encode / decode passes over the same resident rows (no collectives: rows shard naturally)
         z = h.encode(x)
@@ -603,7 +616,7 @@ def main():
                 by_global[str(bs)] = {"rows_per_s": bs * nb / tg_, "us_per_step": 1e6 * tg_ / nb, "rows_per_gpu_per_step": per,
                                       "steps_timed": nb}
             out["train_rows_per_s_by_global_batch"] = by_global
-        if coll and torch.distributed.get_backend() == "nccl" and os.environ.get("BALER_AMD_LIB_COMM", "1") != "0":
+        if lib_comm:
             # ---- what a data-parallel optimiser step costs, as the three-call Python sequence (bamd_fwd_bwd -> torch all-reduce ->
             # bamd_adam_step) and with the communicator INSIDE the library (bamd_train_epoch_dp: the same three stages per batch, one
             # host call per epoch), at 64 and 512 rows per rank.  gpu_us = wall time per step with the stream drained; host_us = the
@@ -712,11 +725,11 @@ def main():
             except OSError as e:       # no scratch space for the file: say so, the line stays valid
                 out["pcie"] = {"error": str(e)}
 
-    if world > 1 or a.c3:
+    if a.c3 or (a.full and world > 1):
         out["c3"] = c3_leg(a, h, flat, m, v, state, world, dev, rank, loss_acc)
         out["c3_train_rows_per_s"] = out["c3"]["train_rows_per_s"]
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_rows)
 
     if rank == 0:

@@ -87,9 +87,27 @@ def test_bench_two_ranks_one_gpu(tmp_path):
     assert d["value"] > 0 and "cpu_baseline" not in d and d["roofline"]["frac"] > 0
 
 
+def test_bench_plain_run_times_the_steps_only(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline keys, the dumped outputs of the last timed step and the roofline of the
+    timed launches, and none of the side measurements that take runs of their own."""
+    env = dict(os.environ)
+    for k in ("BALER_AMD_FORCE_PG", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "BALER_AMD_DIST_BACKEND"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--rows", "65536", "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600)
+    d = _bench_json(r)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "param_checksum", "roofline"):
+        assert key in d, key
+    assert d["value"] > 0 and d["steps"] == 2 and d["warmup"] == 1 and d["roofline"]["frac"] > 0
+    for key in ("encode_rows_per_s", "train_rows_per_s_by_batch", "roofline_extra", "other_configs", "pcie", "c3", "allreduce_us",
+                "cpu_baseline"):
+        assert key not in d, key
+    assert np.load(tmp_path / "out" / "params.npy").shape == (61839,)
+
+
 def test_bench_scale_record_two_ranks_driver_launch():
     """The round-end SCALE run, rehearsed: the driver's own launch line (`python -m torch.distributed.run --nnodes=1
-    --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W`, default extras) with two
+    --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W --full`) with two
     ranks on the one GPU, BALER_AMD_DP_BATCH=per_gpu in the environment as a per-GPU-batch run would have it.  Asserts what the
     SCALE record is computed from -- ONE JSON line from rank 0 with `value`, `rccl_ranks`, `allreduce_us`, both batch policies at
     batch_size 512, bit-identical replicas, the configs[2] leg -- and that every rank wrote its diagnostic lines (device, XCD
@@ -97,7 +115,7 @@ def test_bench_scale_record_two_ranks_driver_launch():
     env = dict(os.environ, BALER_AMD_FORCE_DEVICE="0", BALER_AMD_DIST_BACKEND="gloo", BALER_AMD_DP_BATCH="per_gpu",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = _torchrun(2, [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "65536",
-                      "--c3-rows", "65536", "--pcie-rows", "200000", "--cpu-rows", "20000"], env, free_port())
+                      "--c3-rows", "65536", "--pcie-rows", "200000", "--cpu-rows", "20000", "--full"], env, free_port())
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -224,7 +242,7 @@ def test_bench_spawns_two_ranks_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--rows", "65536", "--c3-rows", "131072"], env=env, capture_output=True, text=True, timeout=900)
+                        "--rows", "65536", "--c3-rows", "131072", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -307,8 +325,8 @@ def _bench_json(r):
 
 
 def test_rccl_world1_bench_step_is_bit_identical():
-    args = [os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--rows", "65536", "--no-extras",
-            "--no-cpu-baseline"]
+    args = [os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--rows", "65536", "--full",
+            "--no-extras", "--no-cpu-baseline"]
     env = dict(os.environ, BALER_AMD_FORCE_PG="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("BALER_AMD_DIST_BACKEND", None)
     env.pop("BALER_AMD_FORCE_DEVICE", None)

@@ -312,3 +312,14 @@ def test_bench_dump_outputs_and_step_count_arguments(tmp_path):
         assert got.dtype == dtype and np.array_equal(got, arrays[name].double().numpy())
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+def test_bench_full_is_opt_in(monkeypatch):
+    """The side measurements run only with --full; a plain run times the steps and prints the line."""
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_cpu_baseline is True and a.steps == 30 and a.warmup == 5

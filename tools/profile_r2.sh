@@ -8,7 +8,7 @@ O=$R/gpurun_out/r2
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 T="timeout 400"
-python3 $R/bench.py > $O/bench.json 2> $O/bench.log
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.log
 B="python3 $R/bench.py --no-cpu-baseline --no-extras"
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- $B > $O/stats.log 2>&1
 $T rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o run -- $B > $O/pmc_f.log 2>&1

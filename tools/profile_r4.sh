@@ -8,7 +8,7 @@ O=$R/gpurun_out/r4p
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 T="timeout 400"
-python3 $R/bench.py > $O/bench.json 2> $O/bench.log
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.log
 B="python3 $R/bench.py --no-cpu-baseline --no-extras"
 PM="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_ANY SQ_WAVE_CYCLES"
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- $B > $O/stats.log 2>&1

@@ -8,7 +8,7 @@ O=$R/gpurun_out/r5p
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 T="timeout 400"
-python3 $R/bench.py > $O/bench.json 2> $O/bench.log
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.log
 B="python3 $R/bench.py --no-cpu-baseline --no-extras"
 PM="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_ANY SQ_WAVE_CYCLES"
 prof() {   # prof TAG COMMAND...: kernel stats + FETCH / WRITE / SQ counter passes

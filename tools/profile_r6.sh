@@ -10,10 +10,10 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 T="timeout 400"
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-python3 $R/bench.py > $O/bench.json 2> $O/bench.log
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.log
 # the same program under a ONE-rank RCCL group (the rank is a child of torchrun, started before anything touches the GPU): dp_step et al.
 BALER_AMD_FORCE_PG=1 timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29513 \
-    $R/bench.py --gpus 1 --no-cpu-baseline > $O/bench_pg.json 2> $O/bench_pg.log
+    $R/bench.py --gpus 1 --full --no-cpu-baseline > $O/bench_pg.json 2> $O/bench_pg.log
 fi
 B="python3 $R/bench.py --no-cpu-baseline --no-extras"
 PM="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_ANY SQ_WAVE_CYCLES"
