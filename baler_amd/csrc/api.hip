@@ -159,8 +159,53 @@ int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device
     return BAMD_OK;
 }
 
+int bamd_create_pjconv(int z_dim, int mode, int device, bamd_handle **out) {
+    BAMD_REQUIRE(out, "null argument");
+    BAMD_REQUIRE(z_dim >= 1 && z_dim <= 2450, "PJ_Conv_AE latent size must be in 1..2450 (encoder.5 = Linear(500, z), decoder.0 = Linear(z, 500))");
+    BAMD_REQUIRE(mode == BAMD_MODE_F32 || mode == BAMD_MODE_F64 || mode == BAMD_MODE_BF16, "unknown mode");
+    if (mode == BAMD_MODE_F64) {
+        set_error("bamd_create_pjconv: PJ_Conv_AE computes in float32 only (the reference model's parameters and 2-D data are float32, "
+                  "training.py:222-227, helper.py:556-558); BAMD_MODE_F64 is not supported");
+        return BAMD_ERR_UNSUPPORTED;
+    }
+    int ndev = bamd_device_count();
+    if (ndev <= 0) {
+        if (ndev == 0) set_error("no HIP device visible");
+        return BAMD_ERR_NO_DEVICE;
+    }
+    BAMD_REQUIRE(device >= 0 && device < ndev, "device ordinal out of range");
+    DeviceGuard guard(device);
+    BAMD_REQUIRE(guard.rc == hipSuccess, "cannot select the device");
+    hipDeviceProp_t prop;
+    BAMD_HIP(hipGetDeviceProperties(&prop, device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        set_error(std::string("libbaler_amd is built for gfx950 only; device is ") + prop.gcnArchName);
+        return BAMD_ERR_NO_DEVICE;
+    }
+    bamd_handle *h = new bamd_handle();
+    h->L = 2;                                  // rows of 784 values in and out, z_dim = dims[L / 2]
+    h->dims = {784, z_dim, 784};
+    h->mode = BAMD_MODE_F32;
+    h->device = device;
+    h->esize = 4;
+    h->nparams = pj_param_count(z_dim);
+    int rc = h->params.ensure((size_t)(h->nparams + 1) * h->esize);
+    if (rc) { delete h; return rc; }
+    rc = pj_setup(h, z_dim);
+    if (rc) { bamd_destroy(h); return rc; }
+    if (mode == BAMD_MODE_BF16) {
+        const char *q = getenv("BALER_AMD_QUIET");
+        if (!(q && q[0] == '1'))
+            fprintf(stderr, "[baler_amd] model PJ_Conv_AE(z=%d): BAMD_MODE_BF16 has kernels for the 24-column AE and the 2500-25 / 625-7 / "
+                            "512-6 wide models only; this handle computes in float32 (fused PJ_Conv_AE kernels)\n", z_dim);
+    }
+    *out = h;
+    return BAMD_OK;
+}
+
 int bamd_path_of(const bamd_handle *h) {
     BAMD_REQUIRE(h, "null handle");
+    if (h->pj_state) return BAMD_PATH_FUSED;
     if (h->fpga_state) return BAMD_PATH_FUSED;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return BAMD_PATH_BF16;
     if (h->mode == BAMD_MODE_F64) return h->fused64_state ? BAMD_PATH_FUSED : BAMD_PATH_GENERIC;
@@ -174,6 +219,7 @@ void bamd_destroy(bamd_handle *h) {
     fused_teardown(h);
     fused64_teardown(h);
     fpga_teardown(h);
+    pj_teardown(h);
     bf16_teardown(h);
     bf16_train_teardown(h);
     comm_teardown(h);
@@ -199,6 +245,7 @@ int bamd_load_params(bamd_handle *h, const void *params, int dtype, void *stream
     int rc = launch_convert(params, dtype, h->params.p, h->esize == 8 ? BAMD_F64 : BAMD_F32, h->nparams, s);
     if (rc) return rc;
     h->params_loaded = true;
+    if (h->pj_state) return BAMD_OK;             // the PJ_Conv_AE kernels read the flat copy itself
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) {
         rc = bf16_pack(h, s);
         h->bf16_infer_stale = false;
@@ -274,6 +321,7 @@ int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, cons
     BAMD_REQUIRE(n_rows >= 0 && ((x && z) || n_rows == 0), "bad arguments");
     if (n_rows == 0) return BAMD_OK;
     hipStream_t s = (hipStream_t)stream;
+    if (h->pj_state) return pj_encode(h, x, x_dtype, n_rows, features, z, z_dtype, s);
     if (int rc = bf16_sync(h, s)) return rc;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return bf16_encode(h, x, x_dtype, n_rows, features, z, z_dtype, s);
     if (h->fpga_state) return fpga_infer(h, 0, x, x_dtype, n_rows, features, z, z_dtype, nullptr, nullptr, nullptr, s);
@@ -291,6 +339,7 @@ int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, cons
     BAMD_REQUIRE(n_rows >= 0 && ((z && out) || n_rows == 0), "bad arguments");
     if (n_rows == 0) return BAMD_OK;
     hipStream_t s = (hipStream_t)stream;
+    if (h->pj_state) return pj_decode(h, z, z_dtype, n_rows, features, int_mask, out, out_dtype, s);
     if (int rc = bf16_sync(h, s)) return rc;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return bf16_decode(h, z, z_dtype, n_rows, features, int_mask, out, out_dtype, s);
     if (h->fpga_state) return fpga_infer(h, 1, z, z_dtype, n_rows, nullptr, out, out_dtype, features, int_mask, nullptr, s);
@@ -307,6 +356,7 @@ int bamd_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows
     BAMD_CHECK_MODEL(h);
     BAMD_REQUIRE(x && loss_sum && n_rows > 0, "bad arguments");
     hipStream_t s = (hipStream_t)stream;
+    if (h->pj_state) return pj_forward_loss(h, x, x_dtype, n_rows, features, recon, recon_dtype, loss_sum, s);
     if (int rc = bf16_sync(h, s)) return rc;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return bf16_forward_loss(h, x, x_dtype, n_rows, features, recon, recon_dtype, loss_sum, s);
     if (h->fpga_state) return fpga_infer(h, 2, x, x_dtype, n_rows, features, recon, recon_dtype, nullptr, nullptr, loss_sum, s);
@@ -327,6 +377,7 @@ int bamd_fwd_bwd(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, con
         BAMD_HIP(hipMemsetAsync(grads, 0, (size_t)(h->nparams + 1) * h->esize, s));
         return BAMD_OK;
     }
+    if (h->pj_state) return pj_step(h, x, x_dtype, n_rows, features, grads, nullptr, nullptr, nullptr, nullptr, nullptr, s);
     if (bf16_kernels_train(h, n_rows)) {
         if (int rc = bf16_train_sync(h, s)) return rc;
         return bf16_fwd_bwd(h, x, x_dtype, n_rows, features, grads, s);
@@ -344,6 +395,10 @@ int bamd_fwd_bwd_latent(bamd_handle *h, const void *x, int x_dtype, int64_t n_ro
                         const void *latent_grad, void *grads, void *stream) {
     BAMD_CHECK_MODEL(h);
     BAMD_REQUIRE(grads && x && n_rows > 0, "bad arguments");
+    if (h->pj_state) {
+        set_error("bamd_fwd_bwd_latent: not implemented for PJ_Conv_AE (the sliced-Wasserstein loss is refused for convolutional models)");
+        return BAMD_ERR_UNSUPPORTED;
+    }
     if (!latent_grad) return bamd_fwd_bwd(h, x, x_dtype, n_rows, features, grads, stream);
     if (fpga_trains(h, n_rows))
         return fpga_step(h, x, x_dtype, n_rows, features, latent_grad, grads, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
@@ -363,6 +418,8 @@ int bamd_adam_step(bamd_handle *h, void *params, const void *grads, void *m, voi
     BAMD_REQUIRE(params && grads && m && v && hp, "null argument");
     BAMD_REQUIRE(hp->step >= 1, "step must be >= 1");
     hipStream_t s = (hipStream_t)stream;
+    if (h->pj_state)
+        return launch_adam(params, h->params.p, grads, m, v, h->nparams, h->esize, *hp, loss_accum, nullptr, nullptr, nullptr, s);
     const int *sc_off = nullptr, *sc_idx = nullptr;
     void *packed = nullptr;
     fused_scatter(h, &sc_off, &sc_idx, &packed);   // Adam also refreshes the packed weight copy (one launch)
@@ -389,6 +446,8 @@ int bamd_train_step(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, 
         if (rc) return rc;
         return bamd_adam_step(h, params, grads, m, v, hp, loss_accum, stream);
     }
+    if (n_rows > 0 && h->pj_state)      // forward + loss + backward, the slab sums, then Adam over the flat vector
+        return pj_step(h, x, x_dtype, n_rows, features, grads, params, m, v, hp, loss_accum, s);
     if (n_rows > 0 && fpga_trains(h, n_rows))      // forward + backward, then the slab sum with Adam: two launches
         return fpga_step(h, x, x_dtype, n_rows, features, nullptr, grads, params, m, v, hp, loss_accum, s);
     if (n_rows > 0 && !bf16_kernels_train(h, n_rows)) {
@@ -481,6 +540,10 @@ int bamd_apply_deltas(void *out, int dtype, int n_cols, const int64_t *rows, con
 int bamd_activation_means(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features,
                           double *out, int max_nodes, void *stream) {
     BAMD_CHECK_MODEL(h);
+    if (h->pj_state) {
+        set_error("bamd_activation_means: PJ_Conv_AE has no activation hooks (the reference model has none either, training.py:287)");
+        return BAMD_ERR_UNSUPPORTED;
+    }
     BAMD_REQUIRE(x && out && n_rows > 0, "bad arguments");
     return generic_activation_means(h, x, x_dtype, n_rows, features, out, max_nodes, (hipStream_t)stream);
 }

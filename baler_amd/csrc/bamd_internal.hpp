@@ -85,6 +85,7 @@ struct bamd_handle {
     bool comm_owned = false;        // created by bamd_comm_init (destroyed with the handle) vs attached by the caller
     int comm_world = 0;
     void *fpga_state = nullptr;     // FPGA_prototype_model shapes with ReLU (fpga.hip)
+    void *pj_state = nullptr;       // PJ_Conv_AE handles (pjconv.hip; bamd_create_pjconv)
 
     bool has_act(int l) const { return !(l == L / 2 - 1 || l == L - 1); }
     bool leaky() const { return act == BAMD_ACT_LEAKY_RELU; }   // the fused / fp64 / bf16 families implement LeakyReLU(0.01) only
@@ -143,6 +144,20 @@ bool fpga_trains(const bamd_handle *h, int64_t n_rows);   // this training batch
 // fwd + loss + bwd (hp == nullptr), or the whole training step with Adam in the second launch; latent_grad may be null
 int fpga_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, const void *latent_grad, void *grads,
               void *params, void *m, void *v, const bamd_adam *hp, double *loss_accum, hipStream_t s);
+
+// ---- pjconv.hip (PJ_Conv_AE on 28 x 28 frames, rows of 784 values, latent 1..2450; float32) ------------------------------------
+int pj_setup(bamd_handle *h, int z);
+void pj_teardown(bamd_handle *h);
+int64_t pj_param_count(int z);
+int pj_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype, hipStream_t s);
+// renorm / int_mask: un-normalise into a float64 output
+int pj_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *renorm, const uint8_t *int_mask, void *out,
+              int out_dtype, hipStream_t s);
+int pj_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *recon, int recon_dtype,
+                    double *loss_sum, hipStream_t s);
+// fwd + loss + bwd into grads ([grads | loss]; null: the handle's scratch), then Adam when hp != nullptr
+int pj_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *grads, void *params, void *m, void *v,
+            const bamd_adam *hp, double *loss_accum, hipStream_t s);
 
 // Sum of n doubles by ONE 256-thread workgroup in a fixed order (bitwise reproducible): 256 strided partial sums, then a fixed
 // tree through `sh` (256 doubles of LDS).  The result is valid in thread 0.  (A single thread adding the partials one after the

@@ -52,7 +52,7 @@ def initialise_model(model_name: str):
         return getattr(models, model_name)
     except AttributeError as e:
         raise AttributeError(
-            f"baler_amd provides the dense models {('AE', 'CFD_dense_AE', 'FPGA_prototype_model')}; got {model_name!r}") from e
+            f"baler_amd provides the models {('AE', 'CFD_dense_AE', 'FPGA_prototype_model', 'PJ_Conv_AE')}; got {model_name!r}") from e
 
 
 def load_model(model_object, model_path: str, n_features: int, z_dim: int):

@@ -255,6 +255,60 @@ def model_saver(model, model_path):
     return data_processing.save_model(model, model_path)
 
 
+CONV_MODELS = ("PJ_Conv_AE",)
+
+
+def is_convolutional(config):
+    return config.data_dimension == 2 and getattr(config, "model_type", None) != "dense"
+
+
+def check_convolutional(config):
+    """The convolutional configurations baler_amd runs: PJ_Conv_AE (reference models.py:668-715) on 28 x 28 frames (after
+    convert_to_blocks) in float32.  Everything else raises here, before the data reaches the GPU."""
+    name = config.model_name
+    if name not in CONV_MODELS:
+        raise NotImplementedError(
+            f"convolutional model {name!r} is out of scope: baler_amd runs PJ_Conv_AE only (Conv_AE / Conv_AE_GDN crash on the "
+            "shipped data, Conv_AE_3D hard-codes a view, TransformerAE has no encode / decode)")
+    shape = npz_array_shape(config.input_path, "data")
+    blocks = getattr(config, "convert_to_blocks", None)
+    frame = (blocks[1], blocks[2]) if blocks else tuple(shape[1:])
+    if tuple(frame) != (28, 28):
+        raise NotImplementedError(f"PJ_Conv_AE runs on 28 x 28 frames only (its Linear(2450, 500) fixes the size); got {tuple(frame)}")
+    from . import models
+    if models._DEFAULT_MODE in ("fp64", "f64"):
+        raise NotImplementedError("PJ_Conv_AE computes in float32 only (the reference model is float32); fp64 mode is not supported")
+    if getattr(config, "custom_loss_function", None) == "loss_function_swae":
+        raise NotImplementedError("the sliced-Wasserstein loss is not supported for PJ_Conv_AE")
+    if getattr(config, "save_error_bounded_deltas", False):
+        raise NotImplementedError("error-bounded deltas are not supported for PJ_Conv_AE")
+    if blocks and getattr(config, "apply_normalization", False):
+        raise NotImplementedError(
+            "convert_to_blocks with apply_normalization is not supported for PJ_Conv_AE: the reference itself fails in decompress "
+            "(operands could not be broadcast together with shapes (16,1,56,56) (28,28))")
+
+
+def save_final_layer(training_path):
+    """training.py:344-346: np.save of np.array(model.get_final_layer_dims()), the decoder's last child -- nn.LeakyReLU(0.2) -- as a
+    0-d object array, which the reference's decompress loads (helper.py:650-653).  Written for that reader; nothing here reads it."""
+    np.save(os.path.join(training_path, "final_layer.npy"), np.array(torch.nn.LeakyReLU(0.2), dtype=object))
+
+
+def load_conv_model(config, model_path, z_dim, part=None):
+    """PJ_Conv_AE from model.pt, or (separate_model_saving) from encoder.pt / decoder.pt.  The reference loads the prefix-free keys
+    of those files with load_state_dict(strict=False) (data_processing.py:108) into a model whose keys carry the encoder. /
+    decoder. prefix, so it loads nothing; here the trained half is actually loaded."""
+    from . import models
+    model = models.PJ_Conv_AE(784, z_dim)
+    model.to(get_device())
+    sd = torch.load(str(model_path), map_location="cpu")
+    if part is None:
+        model.load_state_dict(sd, strict=False)
+    else:
+        model.load_part_state_dict(part, sd)
+    return model
+
+
 def _derive_sizes(config, data_shape, names_len):
     """n_features / latent size exactly as helper.compress derives them (helper.py:505-535)."""
     if config.data_dimension == 1:
@@ -263,8 +317,12 @@ def _derive_sizes(config, data_shape, names_len):
         config.number_of_columns = number_of_columns
         return number_of_columns
     if config.data_dimension == 2:
-        if getattr(config, "model_type", None) != "dense":
-            raise NotImplementedError("baler_amd covers the dense models; convolutional models are out of scope")
+        if is_convolutional(config):
+            # reference baler.py:128-134: the latent size comes from the ORIGINAL frame, even when convert_to_blocks cuts it
+            original = npz_array_shape(config.input_path, "data")
+            config.number_of_columns = original[2]
+            config.latent_space_size = ceil((original[1] * original[2]) / config.compression_ratio)
+            return 784
         number_of_rows = data_shape[1]
         config.number_of_columns = data_shape[2]
         config.latent_space_size = ceil((number_of_rows * config.number_of_columns) / config.compression_ratio)
@@ -303,8 +361,12 @@ def compress(model_path, config):
     if feats is None and flat.dtype != work_dtype:
         flat = flat.to(work_dtype)
 
-    model = data_processing.load_model(data_processing.initialise_model(config.model_name), model_path,
-                                       n_features=n_features, z_dim=config.latent_space_size)
+    if is_convolutional(config):
+        model = load_conv_model(config, model_path, config.latent_space_size,
+                                "encoder" if getattr(config, "separate_model_saving", False) else None)
+    else:
+        model = data_processing.load_model(data_processing.initialise_model(config.model_name), model_path,
+                                           n_features=n_features, z_dim=config.latent_space_size)
     model.eval()
     h = model.handle()
     n_local = flat.shape[0]
@@ -425,8 +487,13 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
     model_dict = torch.load(str(model_path), map_location="cpu")
     number_of_columns = len(model_dict[list(model_dict.keys())[-1]])  # len(de4.bias), helper.py:668-674
 
-    model = data_processing.load_model(data_processing.initialise_model(config.model_name), model_path,
-                                       n_features=number_of_columns, z_dim=latent_space_size)
+    if is_convolutional(config):
+        number_of_columns = 784          # one 28 x 28 frame per row
+        model = load_conv_model(config, model_path, latent_space_size,
+                                "decoder" if getattr(config, "separate_model_saving", False) else None)
+    else:
+        model = data_processing.load_model(data_processing.initialise_model(config.model_name), model_path,
+                                           n_features=number_of_columns, z_dim=latent_space_size)
     model.eval()
     h = model.handle()
     rank, world = bdist.rank_world()
@@ -465,6 +532,8 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
     decompressed = _gather_rows(out, n_total, world, ready)
     if rank != 0:
         return decompressed, names, normalization_features
+    if is_convolutional(config):
+        decompressed = decompressed.reshape((len(decompressed), 1, 28, 28))     # what PJ_Conv_AE.decode returns
     if config.data_dimension == 2 and getattr(config, "model_type", None) == "dense":
         blocks = getattr(config, "convert_to_blocks", None)
         if blocks:

@@ -5,6 +5,8 @@ Mirrors ``baler/modules/models.py`` for the two dense topologies on the hot path
 * ``AE``            (reference models.py:116-183) -- fp64 state dict, 24->200->100->50->z->...->24
 * ``CFD_dense_AE``  (reference models.py:186-253) -- fp32 state dict, same topology, wide ends
 * ``FPGA_prototype_model`` (reference models.py:410-463) -- fp64 state dict, n->20->10->z->10->20->n with ReLU
+* ``PJ_Conv_AE``    (reference models.py:668-715) -- fp32 state dict, 28x28 frames: two strided convolutions, four Linear
+  layers, two transposed convolutions (rows of 784 values on the native side)
 
 Protocol kept: ctor ``(n_features, z_dim)``, ``encode / decode / forward``, ``state_dict`` /
 ``load_state_dict(strict=False)``, ``to``, ``train`` / ``eval``, ``children``, ``parameters``,
@@ -188,13 +190,16 @@ class DenseAE:
                 "call model.to('cuda:0') on a GPU box")
         if self._handle is None:
             with torch.cuda.device(self.flat.device):
-                self._handle = native.Handle(self.dims, self.mode, self.flat.device.index, act=self.act)
+                self._handle = self._new_handle()
             self._dirty = True
         if self._dirty:
             with torch.cuda.device(self.flat.device):
                 self._handle.load_params(self.flat)
             self._dirty = False
         return self._handle
+
+    def _new_handle(self):
+        return native.Handle(self.dims, self.mode, self.flat.device.index, act=self.act)
 
     def mark_params_changed(self):
         self._dirty = True
@@ -277,3 +282,102 @@ class FPGA_prototype_model(DenseAE):
 
     def capture_activations(self, x, features=None):
         raise NotImplementedError("FPGA_prototype_model has no activation hooks (reference models.py:410-463; training.py:287)")
+
+
+# PJ_Conv_AE (reference models.py:668-715): (state-dict key, shape, kind) in module order; kind = how torch's default init draws it
+def pj_conv_layout(z_dim):
+    z = int(z_dim)
+    spec = [("encoder.0", (20, 1, 5, 5)), ("encoder.2", (50, 20, 5, 5)), ("encoder.4", (500, 2450)), ("encoder.5", (z, 500)),
+            ("decoder.0", (500, z)), ("decoder.2", (2450, 500)), ("decoder.4", (50, 20, 5, 5)), ("decoder.5", (20, 1, 5, 5))]
+    out, off = [], 0
+    for name, wshape in spec:
+        # bias length = out channels: dim 0 for Conv2d / Linear, dim 1 for ConvTranspose2d (weight (in, out, kh, kw))
+        nb = wshape[1] if name in ("decoder.4", "decoder.5") else wshape[0]
+        out.append((name + ".weight", off, wshape))
+        off += int(np.prod(wshape))
+        out.append((name + ".bias", off, (nb,)))
+        off += nb
+    return out, off
+
+
+def pj_conv_init(z_dim):
+    """nn.Conv2d / nn.Linear / nn.ConvTranspose2d default init (reset_parameters: kaiming_uniform_(a=sqrt(5)) of the weight, then
+    U(+-1/sqrt(fan_in)) of the bias with fan_in from the weight's dim 1 x receptive field -- for ConvTranspose2d that is its OUT
+    channels) drawn in module order, float32: ``torch.manual_seed(s)`` before construction gives the reference's initial tensors."""
+    parts = []
+    layout, _ = pj_conv_layout(z_dim)
+    for key, _, shape in layout[0::2]:
+        w = torch.empty(shape, dtype=torch.float32)
+        torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+        fan_in, _ = torch.nn.init._calculate_fan_in_and_fan_out(w)
+        bound = 1.0 / math.sqrt(fan_in) if fan_in > 0 else 0.0
+        nb = shape[1] if key.startswith(("decoder.4", "decoder.5")) else shape[0]
+        b = torch.empty(nb, dtype=torch.float32)
+        torch.nn.init.uniform_(b, -bound, bound)
+        parts += [w.reshape(-1), b]
+    return torch.cat(parts)
+
+
+class PJ_Conv_AE(DenseAE):
+    """reference models.PJ_Conv_AE (models.py:668-715): float32 checkpoint with the reference's keys (encoder.0 ... decoder.5).
+    Frames are 28 x 28 (the only size the reference runs end to end); the native side sees one row of 784 values per frame
+    (bamd_create_pjconv).  encode: (N, 1, 28, 28) or (N, 784) -> (N, z); decode / forward -> (N, 1, 28, 28) like the reference.
+    No activation hooks (training.py:287): activation_extraction raises before training starts."""
+    state_dtype = torch.float32
+    act = "leaky_relu"
+    supports_activation_extraction = False
+    FRAME = (1, 28, 28)
+
+    def __init__(self, n_features=784, z_dim=10, *args, mode=None, **kwargs):
+        # n_features is ignored, as by the reference (baler.py passes the frame width): the frame is 28 x 28
+        mode = mode or _DEFAULT_MODE
+        if not 1 <= int(z_dim) <= 2450:
+            raise ValueError(f"PJ_Conv_AE latent size must be in 1..2450; got {z_dim}")
+        if mode in ("fp64", "f64"):
+            raise NotImplementedError("PJ_Conv_AE computes in float32 only (the reference model is float32); fp64 mode is not supported")
+        self.n_features = native.PJ_FEATURES
+        self.z_dim = int(z_dim)
+        self.dims = [self.n_features, self.z_dim, self.n_features]
+        self.mode = mode
+        self.layout, self.nparams = pj_conv_layout(z_dim)
+        self.param_dtype = torch.float32
+        self.flat = torch.zeros(self.nparams + 1, dtype=torch.float32)
+        self.flat[: self.nparams] = pj_conv_init(z_dim)
+        self.training = True
+        self.activations = {}
+        self._hooks_on = False
+        self._handle = None
+        self._dirty = True
+
+    def _new_handle(self):
+        return native.Handle.pj_conv(self.z_dim, self.mode, self.flat.device.index)
+
+    def children(self):
+        return iter([])     # no per-layer views: the loss has no L1 term (validate=True) and the model no hooks
+
+    def decode(self, z):
+        return super().decode(z).view(-1, *self.FRAME)
+
+    def forward(self, x):
+        return super().forward(x).view(-1, *self.FRAME)
+
+    __call__ = forward
+
+    def encoder_state_dict(self):
+        """What the reference's encoder_saver writes (data_processing.py:50-60): model.encoder's own keys, 0.weight ... 5.bias."""
+        return OrderedDict((k[len("encoder."):], v) for k, v in self.state_dict().items() if k.startswith("encoder."))
+
+    def decoder_state_dict(self):
+        return OrderedDict((k[len("decoder."):], v) for k, v in self.state_dict().items() if k.startswith("decoder."))
+
+    def load_part_state_dict(self, part, sd):
+        """Load encoder.pt / decoder.pt (prefix-free keys) into that half of the model."""
+        if part not in ("encoder", "decoder"):
+            raise ValueError(part)
+        return self.load_state_dict(OrderedDict((f"{part}.{k}", v) for k, v in sd.items()), strict=False)
+
+    def store_hooks(self):
+        raise NotImplementedError("PJ_Conv_AE has no activation hooks (reference models.py:668-715; training.py:287)")
+
+    def capture_activations(self, x, features=None):
+        raise NotImplementedError("PJ_Conv_AE has no activation hooks (reference models.py:668-715; training.py:287)")

@@ -221,9 +221,7 @@ def _to_device_dataset(arr, config, device):
     if isinstance(arr, ShardedRows):
         return arr.map_local(lambda t: _to_device_dataset(t, config, device))
     t = arr if isinstance(arr, torch.Tensor) else torch.as_tensor(np.asarray(arr))
-    if config.data_dimension == 2:
-        if getattr(config, "model_type", None) != "dense":
-            raise NotImplementedError("baler_amd covers the dense models; convolutional models are out of scope")
+    if config.data_dimension == 2:      # dense and convolutional (PJ_Conv_AE: one 28 x 28 frame per row) alike
         t = t.to(torch.float32).reshape(t.shape[0], -1)
     elif config.data_dimension == 1:
         t = t.to(torch.float64)

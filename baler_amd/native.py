@@ -27,8 +27,9 @@ SYMBOLS = (
     "bamd_adam_step", "bamd_train_step", "bamd_emd_rows", "bamd_activation_means",
     "bamd_error_deltas", "bamd_apply_deltas", "bamd_fwd_bwd_latent", "bamd_swd", "bamd_col_minmax", "bamd_path_of",
     "bamd_train_epoch", "bamd_comm_unique_id", "bamd_comm_init", "bamd_comm_attach", "bamd_comm_release", "bamd_comm_world",
-    "bamd_allreduce_sum", "bamd_train_epoch_dp", "bamd_create_act", "bamd_act_of",
+    "bamd_allreduce_sum", "bamd_train_epoch_dp", "bamd_create_act", "bamd_act_of", "bamd_create_pjconv",
 )
+PJ_FEATURES = 784      # PJ_Conv_AE: one 28 x 28 frame per row
 
 
 class NativeError(RuntimeError):
@@ -62,6 +63,7 @@ def lib():
     L.bamd_create.argtypes = [ctypes.POINTER(ci), ci, ci, ci, ctypes.POINTER(vp)]
     L.bamd_create_act.argtypes = [ctypes.POINTER(ci), ci, ci, ci, ci, ctypes.POINTER(vp)]
     L.bamd_act_of.argtypes = [vp]
+    L.bamd_create_pjconv.argtypes = [ci, ci, ci, ctypes.POINTER(vp)]
     L.bamd_act_of.restype = ci
     L.bamd_destroy.argtypes = [vp]
     L.bamd_destroy.restype = None
@@ -275,6 +277,23 @@ class Handle:
         self.param_dtype = torch.float64 if self.mode == MODE_F64 else torch.float32
         # the mode the library computes in: "bf16" asked of a shape without bf16 kernels is served in float32 (notice on stderr)
         self.compute_mode = int(lib().bamd_mode_of(h))
+
+    @classmethod
+    def pj_conv(cls, z_dim, mode="fp32", device=None):
+        """Handle of PJ_Conv_AE (bamd_create_pjconv): rows of 784 values (one 28 x 28 frame each) in and out, latent z_dim
+        (1..2450); every row-based method works unchanged.  "bf16" computes in float32 (notice on stderr), "fp64" is refused."""
+        require_gpu()
+        self = cls.__new__(cls)
+        self.dims = [PJ_FEATURES, int(z_dim), PJ_FEATURES]
+        self.mode = MODE_NAMES[mode] if isinstance(mode, str) else int(mode)
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        h = ctypes.c_void_p()
+        _check(lib().bamd_create_pjconv(int(z_dim), self.mode, self.device.index, ctypes.byref(h)), "bamd_create_pjconv")
+        self._h = h
+        self.nparams = int(lib().bamd_param_count(h))
+        self.param_dtype = torch.float32
+        self.compute_mode = int(lib().bamd_mode_of(h))
+        return self
 
     @property
     def act(self):

@@ -110,6 +110,26 @@ typedef enum bamd_act {
 int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device, bamd_handle **out);
 int bamd_act_of(const bamd_handle *h);     /* the handle's bamd_act, or BAMD_ERR_INVALID for a null handle */
 
+/* PJ_Conv_AE, the reference's convolutional autoencoder for 28 x 28 frames.  Replaces: models.PJ_Conv_AE.__init__ / encode / decode /
+ * forward (models.py:668-715) and data_processing.initialise_model / load_model (data_processing.py:76-110) for that model:
+ *   encoder.0 Conv2d(1, 20, 5, stride 2, pad 2) 28x28 -> 14x14, LeakyReLU(0.2); encoder.2 Conv2d(20, 50, 5, 2, 2) -> 7x7; flatten;
+ *   encoder.4 Linear(2450, 500); encoder.5 Linear(500, z);  decoder.0 Linear(z, 500), LeakyReLU(0.2); decoder.2 Linear(500, 2450);
+ *   decoder.4 ConvTranspose2d(50, 20, 5, 2, 2, output_padding 1) -> 14x14; decoder.5 ConvTranspose2d(20, 1, 5, 2, 2, 1) -> 28x28,
+ *   LeakyReLU(0.2).
+ * An image is ONE ROW of 784 values (NCHW (N, 1, 28, 28) is row-major (N, 784)), so every row-based call below takes rows of 784
+ * values with the usual signature; features / renorm are per pixel, (2, 784) float64.  The flat parameter vector is the state-dict
+ * order of the reference (per tensor weight row-major then bias; ConvTranspose2d weights are (in, out, kh, kw)): 2504541 + 1001 z
+ * parameters.  The loss of bamd_forward_loss / bamd_fwd_bwd is utils.mse_sum_loss_l1(validate=True) (utils.py:176-211) of the
+ * reference's 2-D path, whose divisor is true_data.shape[1] = the channel count, 1: the PLAIN sum of squared errors, not divided by 784.
+ * Arithmetic: v_mfma_f32_16x16x4_f32 (exact fp32) implicit GEMMs, fixed-order weight-gradient sums: bitwise repeatable.
+ * z_dim: 1 .. 2450 (else BAMD_ERR_INVALID).  mode: BAMD_MODE_F32; BAMD_MODE_BF16 gives a float32 handle with a notice on stderr
+ * (bamd_mode_of() reports BAMD_MODE_F32); BAMD_MODE_F64 returns BAMD_ERR_UNSUPPORTED.  Served on such a handle: bamd_encode,
+ * bamd_decode (with the un-normalise / int-mask epilogue), bamd_forward_loss, bamd_fwd_bwd, bamd_adam_step, bamd_train_step,
+ * bamd_train_epoch, bamd_train_epoch_dp (and the communicator calls), bamd_load_params, bamd_param_count, bamd_path_of
+ * (BAMD_PATH_FUSED).  bamd_activation_means (the reference model has no hooks, training.py:287) and bamd_fwd_bwd_latent return
+ * BAMD_ERR_UNSUPPORTED. */
+int bamd_create_pjconv(int z_dim, int mode, int device, bamd_handle **out);
+
 /* Which kernels serve this handle's throughput calls (bamd_encode / bamd_decode / bamd_fwd_bwd at large batches).  The fused
  * register-chained / wide-layer kernels are template instantiations.  EXACT instantiations for the shapes the reference ships configs
  * for: AE(24, z) for z in {15, 12, 10, 8, 6, 5, 4, 3, 2} (models.py:116-183 at the compression ratios of baler.py:117-123),
