@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -159,14 +160,42 @@ int pj_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const
 int pj_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *grads, void *params, void *m, void *v,
             const bamd_adam *hp, double *loss_accum, hipStream_t s);
 
-// Sum of n doubles by ONE 256-thread workgroup in a fixed order (bitwise reproducible): 256 strided partial sums, then a fixed
-// tree through `sh` (256 doubles of LDS).  The result is valid in thread 0.  (A single thread adding the partials one after the
-// other -- what every loss reduction here did first -- is a chain of dependent L2 round trips: 6.5 us for 32 partials.)
+// ---- one Adam step ----------------------------------------------------------------------------------------------------------
+// The scalars every parameter of a step shares.  adam_scalars() holds the only bias-correction arithmetic of the library and
+// adam_update() the only per-element update: adam_k (elementwise.hip) and the weight-gradient kernels that apply Adam to the
+// parameters they own inline the same operations in the same order (-ffp-contract=off), so bamd_train_step ==
+// bamd_fwd_bwd + bamd_adam_step to the last bit on every kernel family.
+struct AdamScalars {
+    double b1, b2, eps, step_size, bc2_sqrt;
+};
+inline AdamScalars adam_scalars(const bamd_adam &hp) {
+    const double bc1 = 1.0 - pow(hp.beta1, (double)hp.step);
+    const double bc2 = 1.0 - pow(hp.beta2, (double)hp.step);
+    return {hp.beta1, hp.beta2, hp.eps, hp.lr / bc1, sqrt(bc2)};
+}
+
 #if defined(__HIPCC__)
-__device__ __forceinline__ double block_sum_fixed(const double *__restrict__ part, int n, double *sh) {
-    double s = 0.0;
-    for (int k = threadIdx.x; k < n; k += 256) s += part[k];
-    sh[threadIdx.x] = s;
+// torch.optim.Adam single-tensor step (training.py:266; torch/optim/adam.py _single_tensor_adam) of one element.  The arithmetic
+// runs in float64 and m, v and the returned parameter are rounded to the storage type once, so the fp32 mode differs from the
+// fp64 reference by storage rounding only.
+template <typename T>
+__device__ __forceinline__ T adam_update(const AdamScalars &a, T g, T &m, T &v, T p) {
+    const double gi = (double)g;
+    double mi = (double)m, vi = (double)v;
+    mi = mi + (gi - mi) * (1.0 - a.b1);            // exp_avg.lerp_(grad, 1 - beta1)
+    vi = vi * a.b2 + (1.0 - a.b2) * gi * gi;       // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1-beta2)
+    const double denom = sqrt(vi) / a.bc2_sqrt + a.eps;
+    const double pi = (double)p - a.step_size * (mi / denom);
+    m = (T)mi;
+    v = (T)vi;
+    return (T)pi;
+}
+
+// ---- fixed-order sums of ONE 256-thread workgroup (bitwise reproducible) ------------------------------------------------------
+// One double per thread through a fixed tree in `sh` (256 doubles of LDS); every thread returns the sum.  A caller whose `sh`
+// aliases LDS still being read puts its own barrier in front.
+__device__ __forceinline__ double block_sum_tree(double v, double *sh) {
+    sh[threadIdx.x] = v;
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
         if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
@@ -174,5 +203,22 @@ __device__ __forceinline__ double block_sum_fixed(const double *__restrict__ par
     }
     return sh[0];
 }
+// Sum of n doubles in memory: 256 strided partial sums, then the tree.  (A single thread adding the partials one after the
+// other -- what every loss reduction here did first -- is a chain of dependent L2 round trips: 6.5 us for 32 partials.)
+__device__ __forceinline__ double block_sum_fixed(const double *__restrict__ part, int n, double *sh) {
+    double s = 0.0;
+    for (int k = threadIdx.x; k < n; k += 256) s += part[k];
+    return block_sum_tree(s, sh);
+}
+// The finishing launch of a loss: one workgroup, *dst = (or +=) scale * sum of the partials.  (Internal linkage: every
+// translation unit that launches it registers its own copy, like the kernels of its own file.)
+namespace {
+template <typename TO>
+__global__ void __launch_bounds__(256) sum_partials_fixed_k(const double *__restrict__ part, int n, double scale, TO *dst, int accumulate) {
+    __shared__ double sh[256];
+    const double s = block_sum_fixed(part, n, sh) * scale;
+    if (threadIdx.x == 0) *dst = accumulate ? (TO)((double)*dst + s) : (TO)s;
+}
+}  // namespace
 #endif
 }  // namespace bamd

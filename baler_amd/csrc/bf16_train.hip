@@ -888,13 +888,8 @@ __global__ void __launch_bounds__(256) bf16_train_kernel(const uint4 *__restrict
     if constexpr (P::fwd_end == 8) {   // per-workgroup loss partial (fixed-order tree), stored after the tiles
         __syncthreads();
         double *sh = (double *)lds_raw;
-        sh[threadIdx.x] = lacc;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) ((double *)(slabs + (int64_t)loss_tile * gridDim.x * 64))[blockIdx.x] = sh[0];
+        const double wsum = block_sum_tree(lacc, sh);
+        if (threadIdx.x == 0) ((double *)(slabs + (int64_t)loss_tile * gridDim.x * 64))[blockIdx.x] = wsum;
     }
 }
 

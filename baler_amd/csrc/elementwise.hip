@@ -230,13 +230,8 @@ __global__ void __launch_bounds__(256) emd_partial(const T *__restrict__ x, cons
         acc += sacc / (double)c;
     }
     __shared__ double sh[256];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
+    const double s = block_sum_tree(acc, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __global__ void sum_partials_k(const double *__restrict__ part, int n, double *__restrict__ out,
@@ -329,32 +324,25 @@ int launch_apply_deltas(void *out, int dtype, int n_cols, const int64_t *rows, c
 }
 
 // ---- fused Adam ---------------------------------------------------------------------------------
-// torch.optim.Adam single-tensor step (training.py:266; torch/optim/adam.py _single_tensor_adam) over
-// ONE flat buffer: p, g, m, v are read once and p, m, v written once (28 B/param in fp32).  The
-// per-element arithmetic runs in float64 and is rounded to the storage type once, so the fp32 mode
-// differs from the fp64 reference by storage rounding only.  zero_grad needs no work: the next
-// bamd_fwd_bwd overwrites the gradient buffer.
+// adam_update (bamd_internal.hpp) over ONE flat buffer: p, g, m, v are read once and p, m, v written
+// once (28 B/param in fp32).  zero_grad needs no work: the next bamd_fwd_bwd overwrites the gradient
+// buffer.
 template <typename T>
 __global__ void __launch_bounds__(256) adam_k(T *__restrict__ p, T *__restrict__ pcopy,
                                               const T *__restrict__ g, T *__restrict__ m,
-                                              T *__restrict__ v, int64_t np, double b1, double b2,
-                                              double eps, double step_size, double bc2_sqrt,
+                                              T *__restrict__ v, int64_t np, AdamScalars a,
                                               double *loss_accum, const int *__restrict__ sc_off,
                                               const int *__restrict__ sc_idx, T *__restrict__ packed) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < np) {
-        double gi = (double)g[i];
-        double mi = (double)m[i], vi = (double)v[i];
-        mi = mi + (gi - mi) * (1.0 - b1);          // exp_avg.lerp_(grad, 1 - beta1)
-        vi = vi * b2 + (1.0 - b2) * gi * gi;       // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1-beta2)
-        double denom = sqrt(vi) / bc2_sqrt + eps;
-        double pi = (double)p[i] - step_size * (mi / denom);
-        m[i] = (T)mi;
-        v[i] = (T)vi;
-        p[i] = (T)pi;
-        if (pcopy) pcopy[i] = (T)pi;
+        T mi = m[i], vi = v[i];
+        const T pi = adam_update(a, g[i], mi, vi, p[i]);
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi;
+        if (pcopy) pcopy[i] = pi;
         if (packed)   // refresh every copy of this parameter in the MFMA-fragment-packed buffer (fused pack)
-            for (int k = sc_off[i]; k < sc_off[i + 1]; ++k) packed[sc_idx[k]] = (T)pi;
+            for (int k = sc_off[i]; k < sc_off[i + 1]; ++k) packed[sc_idx[k]] = pi;
     }
     if (loss_accum && i == 0) *loss_accum += (double)g[np];
 }
@@ -362,17 +350,14 @@ __global__ void __launch_bounds__(256) adam_k(T *__restrict__ p, T *__restrict__
 int launch_adam(void *params, void *pcopy, const void *grads, void *m, void *v, int64_t np,
                 size_t esize, const bamd_adam &hp, double *loss_accum, const int *sc_off, const int *sc_idx,
                 void *packed, hipStream_t s) {
-    double bc1 = 1.0 - pow(hp.beta1, (double)hp.step);
-    double bc2 = 1.0 - pow(hp.beta2, (double)hp.step);
-    double step_size = hp.lr / bc1;
-    double bc2_sqrt = sqrt(bc2);
+    const AdamScalars a = adam_scalars(hp);
     dim3 g((unsigned)((np + 255) / 256)), b(256);
     if (esize == 8)
         hipLaunchKernelGGL(adam_k<double>, g, b, 0, s, (double *)params, (double *)pcopy, (const double *)grads,
-                           (double *)m, (double *)v, np, hp.beta1, hp.beta2, hp.eps, step_size, bc2_sqrt, loss_accum, sc_off, sc_idx, (double *)packed);
+                           (double *)m, (double *)v, np, a, loss_accum, sc_off, sc_idx, (double *)packed);
     else
         hipLaunchKernelGGL(adam_k<float>, g, b, 0, s, (float *)params, (float *)pcopy, (const float *)grads,
-                           (float *)m, (float *)v, np, hp.beta1, hp.beta2, hp.eps, step_size, bc2_sqrt, loss_accum, sc_off, sc_idx, (float *)packed);
+                           (float *)m, (float *)v, np, a, loss_accum, sc_off, sc_idx, (float *)packed);
     BAMD_HIP(hipGetLastError());
     return BAMD_OK;
 }

@@ -9,7 +9,7 @@
 // Training: the forward activations of the tile stay in LDS; the backward pass walks the layers from de3 to en1, and once a layer's
 // dL/d pre-activation is in LDS the workgroup reduces dW_l = dZ_l^T Y_{l-1} and db_l over the tile's 64 rows into registers (thread t
 // owns the parameters t + 256 i) while it forms the previous layer's dL/d pre-activation.  Each workgroup writes one partial-gradient
-// slab and one loss partial; a second launch sums the slabs in workgroup order (and optionally runs Adam with adam_k's arithmetic):
+// slab and one loss partial; a second launch sums the slabs in workgroup order (and optionally runs Adam: adam_update):
 // no float atomics, results are bitwise repeatable, and a training step is two launches at any batch size.
 #include <algorithm>
 #include <cmath>
@@ -220,14 +220,6 @@ __global__ void __launch_bounds__(NT) fpga_infer_k(int kind, int n, int z, const
     }
 }
 
-// loss partials -> *dst = sum / n_cols (one 256-thread workgroup, fixed order)
-template <typename TO>
-__global__ void __launch_bounds__(256) fpga_loss_final_k(const double *__restrict__ part, int nblk, double scale, TO *dst) {
-    __shared__ double sh[256];
-    const double s = block_sum_fixed(part, nblk, sh);
-    if (threadIdx.x == 0) *dst = (TO)(s * scale);
-}
-
 // fwd + loss + bwd of the rows of this workgroup's tiles -> one partial-gradient slab (np entries) + one loss partial
 template <typename T>
 __global__ void __launch_bounds__(NT) fpga_fwd_bwd_k(int n, int z, const void *x, int x_f64, int64_t n_rows, const double *features,
@@ -310,10 +302,10 @@ __global__ void __launch_bounds__(NT) fpga_fwd_bwd_k(int n, int z, const void *x
 
 struct FpgaAdam {
     int on;
-    double b1, b2, eps, step_size, bc2_sqrt;
+    AdamScalars s;
 };
 
-// slabs -> gradient (workgroup order), loss; with Adam on: the optimiser step of adam_k (elementwise.hip) on the summed gradient
+// slabs -> gradient (workgroup order), loss; with Adam on: the optimiser step on the summed gradient
 template <typename T>
 __global__ void __launch_bounds__(256) fpga_reduce_k(const T *__restrict__ part, int nblk, int64_t part_stride, int np,
                                                      const double *__restrict__ loss_part, double loss_scale, T *grads,
@@ -333,16 +325,12 @@ __global__ void __launch_bounds__(256) fpga_reduce_k(const T *__restrict__ part,
     for (int b = 0; b < nblk; ++b) g += part[(int64_t)b * part_stride + i];
     if (grads) grads[i] = g;
     if (!ad.on) return;
-    const double gi = (double)g;
-    double mi = (double)m[i], vi = (double)v[i];
-    mi = mi + (gi - mi) * (1.0 - ad.b1);
-    vi = vi * ad.b2 + (1.0 - ad.b2) * gi * gi;
-    const double denom = sqrt(vi) / ad.bc2_sqrt + ad.eps;
-    const double pi = (double)params[i] - ad.step_size * (mi / denom);
-    m[i] = (T)mi;
-    v[i] = (T)vi;
-    params[i] = (T)pi;
-    pcopy[i] = (T)pi;
+    T mi = m[i], vi = v[i];
+    const T pi = adam_update(ad.s, g, mi, vi, params[i]);
+    m[i] = mi;
+    v[i] = vi;
+    params[i] = pi;
+    pcopy[i] = pi;
 }
 
 struct FpgaState {
@@ -384,8 +372,8 @@ int infer_T(bamd_handle *h, int kind, const void *in, int in_dtype, int64_t n_ro
                        (double *)st->lossp.p);
     BAMD_HIP(hipGetLastError());
     if (kind == 2) {
-        hipLaunchKernelGGL(fpga_loss_final_k<double>, dim3(1), dim3(256), 0, s, (const double *)st->lossp.p, grid, 1.0 / st->n,
-                           loss_sum);
+        hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)st->lossp.p, grid, 1.0 / st->n,
+                           loss_sum, 0);
         BAMD_HIP(hipGetLastError());
     }
     return BAMD_OK;
@@ -406,11 +394,9 @@ int step_T(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const dou
                        (const T *)h->params.p, (const T *)latent_grad, (T *)st->part.p, stride, (double *)st->lossp.p);
     BAMD_HIP(hipGetLastError());
     FpgaAdam ad{};
-    if (hp) {     // the scalars of launch_adam (elementwise.hip)
+    if (hp) {
         ad.on = 1;
-        ad.b1 = hp->beta1; ad.b2 = hp->beta2; ad.eps = hp->eps;
-        ad.step_size = hp->lr / (1.0 - pow(hp->beta1, (double)hp->step));
-        ad.bc2_sqrt = sqrt(1.0 - pow(hp->beta2, (double)hp->step));
+        ad.s = adam_scalars(*hp);
     }
     hipLaunchKernelGGL(fpga_reduce_k<T>, dim3((o.np + 255) / 256), dim3(256), 0, s, (const T *)st->part.p, grid, stride, o.np,
                        (const double *)st->lossp.p, 1.0 / st->n, (T *)grads, ad, (T *)params, (T *)h->params.p, (T *)m, (T *)v,

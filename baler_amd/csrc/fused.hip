@@ -558,13 +558,8 @@ __global__ void __launch_bounds__(256) infer_kernel(const v4 *packed, const void
         ring_tail<S::total>(ring, ws);
     }
     if (KIND == K_FORWARD) {
-        sh[threadIdx.x] = lacc;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) loss_part[blockIdx.x] = sh[0];
+        const double wsum = block_sum_tree(lacc, sh);
+        if (threadIdx.x == 0) loss_part[blockIdx.x] = wsum;
     }
 }
 
@@ -1778,13 +1773,8 @@ __global__ void __launch_bounds__(256) wide_train_fwd_kernel(const v4 *packed, c
             }, fr);
     }
     if constexpr (MID) return;
-    sh[threadIdx.x] = lacc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss_part[blockIdx.x] = sh[0];
+    const double wsum = block_sum_tree(lacc, sh);
+    if (threadIdx.x == 0) loss_part[blockIdx.x] = wsum;
 }
 
 // ---- wide models, SMALL training batches (the reference's own: CFD_project_still trains with batch_size = 60, exafel 1 .. 36, hurricane
@@ -1905,13 +1895,8 @@ __global__ void __launch_bounds__(256) wide_small_out_kernel(const v4 *packed, c
                 else if (dz8) wide_store_tile<F, FL, WRT>(o, dz8, out_f64, row, t, g, fr);
             }
         }, fr, t0, t1);
-    sh[threadIdx.x] = lacc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
+    const double wsum = block_sum_tree(lacc, sh);
+    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = wsum;
 }
 
 // The same for FEW rows (<= in16_rows()): ONE 16-row tile per workgroup (blockIdx.y), its four waves deal the tiles of the range among
@@ -1964,13 +1949,8 @@ __global__ void __launch_bounds__(256) wide_small_out16_kernel(const v4 *packed,
             }
         }
     }
-    sh[threadIdx.x] = lacc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
+    const double wsum = block_sum_tree(lacc, sh);
+    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = wsum;
 }
 
 // the input-gradient chain of 16 rows per wave: dZ_6 = (dZ_7 W_7) * lrelu'(y7) streamed over the wide dimension, then layers 6..1
@@ -2355,13 +2335,8 @@ __global__ void __launch_bounds__(256) wide_bf16_train_fwd_kernel(const v4 *pack
             }
         }
     }
-    sh[threadIdx.x] = lacc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss_part[blockIdx.x] = sh[0];
+    const double wsum = block_sum_tree(lacc, sh);
+    if (threadIdx.x == 0) loss_part[blockIdx.x] = wsum;
 }
 
 // the input-gradient chain of 2 x 16 rows per wave: dZ_6 = (dZ_7 W_7) * lrelu'(y7) with the wide product on the bf16 MFMA (fragments of
@@ -2700,14 +2675,8 @@ __global__ void __launch_bounds__(256) train_dec_kernel(const v4 *packed, const 
 #endif
     // per-workgroup loss partial (fixed-order tree)
     __syncthreads();
-    double *sh = (double *)lds;
-    sh[threadIdx.x] = lacc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) ((double *)(slabs + (int64_t)N::slab_off(N::L) * gridDim.x * 64))[blockIdx.x] = sh[0];   // loss partials after the tiles
+    const double wsum = block_sum_tree(lacc, (double *)lds);
+    if (threadIdx.x == 0) ((double *)(slabs + (int64_t)N::slab_off(N::L) * gridDim.x * 64))[blockIdx.x] = wsum;   // loss partials after the tiles
 }
 
 #if BAMD_SPLIT == 2
@@ -3474,11 +3443,11 @@ __global__ void __launch_bounds__(256) lat4_chain_kernel(const v4 *__restrict__ 
     if (threadIdx.x == 0) loss_part[4 * blk + quad] = ((loss_lds[0] + loss_lds[1]) + loss_lds[2]) + loss_lds[3];
 }
 
-struct AdamArgs {   // scalars of one Adam step (launch_adam's), and where the state lives
+struct AdamArgs {   // where the state of one Adam step lives, and its scalars
     float *params, *pcopy, *m, *v, *packed;
     const int *sc_off, *sc_idx;
     double *loss_accum;
-    double b1, b2, eps, step_size, bc2_sqrt;
+    AdamScalars s;
 };
 
 // grid = 8 x ceil((dW tiles + 1) / 8).  A block contracts dZ^T (tile nt of layer l) with X (tile kt) over all 16-row
@@ -3508,17 +3477,9 @@ __global__ void __launch_bounds__(256) lat2_dw_kernel(const float *__restrict__ 
     if (tile == T) {   // loss: fixed-order sum of the per-block partials, / C
         // 256 strided sums, then a fixed tree (ONE thread adding 32 .. 128 partials one dependent L2 round trip after the other
         // was the longest workgroup of this kernel: 6.5 us of its 6.5-9 us)
-        double *lred = (double *)red;
-        double s = 0.0;
-        for (int k = threadIdx.x; k < nloss; k += 256) s += loss_part[k];
-        lred[threadIdx.x] = s;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) lred[threadIdx.x] += lred[threadIdx.x + st];
-            __syncthreads();
-        }
+        const double s = block_sum_fixed(loss_part, nloss, (double *)red);
         if (threadIdx.x == 0) {
-            const float gl = (float)(lred[0] * inv_c);
+            const float gl = (float)(s * inv_c);
             if (grads) grads[np] = MODE == DW_ACCUM ? grads[np] + gl : gl;
             if (MODE == DW_ADAM && ad.loss_accum) *ad.loss_accum += (double)gl;
         }
@@ -3583,15 +3544,10 @@ __global__ void __launch_bounds__(256) lat2_dw_kernel(const float *__restrict__ 
     }
     if (p < 0) return;
     if (grads) grads[p] = MODE == DW_ACCUM ? grads[p] + gsum : gsum;
-    if (MODE == DW_ADAM) {   // elementwise.hip adam_k, on the 256 parameters this tile owns
-        const double gi = (double)gsum;
-        double mi = (double)pm, vi = (double)pv;
-        mi = mi + (gi - mi) * (1.0 - ad.b1);
-        vi = vi * ad.b2 + (1.0 - ad.b2) * gi * gi;
-        const double denom = sqrt(vi) / ad.bc2_sqrt + ad.eps;
-        const float pn = (float)((double)pp - ad.step_size * (mi / denom));
-        ad.m[p] = (float)mi;
-        ad.v[p] = (float)vi;
+    if (MODE == DW_ADAM) {   // on the 256 parameters this tile owns
+        const float pn = adam_update(ad.s, gsum, pm, pv, pp);
+        ad.m[p] = pm;
+        ad.v[p] = pv;
         ad.params[p] = pn;
         if (ad.pcopy) ad.pcopy[p] = pn;
 #pragma unroll
@@ -3646,26 +3602,6 @@ __global__ void __launch_bounds__(256) pack_k(const float *__restrict__ params, 
         int s = src[i];
         packed[i] = s >= 0 ? params[s] : 0.f;
     }
-}
-
-__global__ void __launch_bounds__(256) sum_loss_k(const double *__restrict__ part, int n, double scale, double *__restrict__ out) {
-    __shared__ double sh[256];
-    const double s = block_sum_fixed(part, n, sh);
-    if (threadIdx.x == 0) *out = s * scale;
-}
-
-// the same for thousands of partials: 256 strided fixed-order sums, then a fixed tree
-__global__ void __launch_bounds__(256) sum_loss_wide_k(const double *__restrict__ part, int n, double scale, double *__restrict__ out) {
-    __shared__ double sh[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sh[0] * scale;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
@@ -3908,7 +3844,7 @@ template <int F, int Z, bool RT = false> struct Impl {
         hipLaunchKernelGGL((infer_kernel<F, Z, K_FORWARD, RT>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p, x,
                            x_dtype == BAMD_F64, n, features, recon, recon_dtype == BAMD_F64, (const uint8_t *)nullptr,
                            (double *)h->lossp.p, fr(h), zr(h));
-        hipLaunchKernelGGL(sum_loss_k, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, grid, 1.0 / fr(h), loss_sum);
+        hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, grid, 1.0 / fr(h), loss_sum, 0);
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
@@ -4284,7 +4220,7 @@ template <int F, int Z, bool WRT = false> struct ImplWide {
                                recon_dtype == BAMD_F64, (double *)h->lossp.p + nblk, fr, zr);
             nblk += grid;
         }
-        hipLaunchKernelGGL(sum_loss_wide_k, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, nblk, 1.0 / fr, loss_sum);
+        hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, nblk, 1.0 / fr, loss_sum, 0);
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
@@ -4835,9 +4771,7 @@ static int train_step_on(bamd_handle *h, const void *x, int x_dtype, int64_t n, 
     ad.packed = (float *)h->packed.p;
     ad.sc_off = (const int *)st->sc_off.p; ad.sc_idx = (const int *)st->sc_idx.p;
     ad.loss_accum = loss_accum;
-    ad.b1 = hp.beta1; ad.b2 = hp.beta2; ad.eps = hp.eps;      // same scalars as launch_adam (elementwise.hip)
-    ad.step_size = hp.lr / (1.0 - pow(hp.beta1, (double)hp.step));
-    ad.bc2_sqrt = sqrt(1.0 - pow(hp.beta2, (double)hp.step));
+    ad.s = adam_scalars(hp);
     return st->ops->train_step(h, x, x_dtype, n, features, grads, ad, s);
 }
 

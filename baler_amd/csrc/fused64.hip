@@ -401,7 +401,7 @@ struct Adam64 {
     double *params, *pcopy, *m, *v, *packed;
     const int *sc_off, *sc_idx;
     double *loss_accum;
-    double b1, b2, eps, step_size, bc2_sqrt;
+    AdamScalars s;
 };
 
 // one workgroup per weight-gradient tile: contracts dZ^T (tile nt of layer l) with [X | 1] (tile kt) over all 16-row blocks
@@ -499,14 +499,10 @@ __global__ void __launch_bounds__(256) dw64_kernel(const double *__restrict__ im
     }
     if (p < 0) return;
     if (grads) grads[p] = gsum;
-    if (MODE == DW_ADAM) {   // elementwise.hip adam_k, on the parameters this tile owns
-        double mi = pm, vi = pv;
-        mi = mi + (gsum - mi) * (1.0 - ad.b1);
-        vi = vi * ad.b2 + (1.0 - ad.b2) * gsum * gsum;
-        const double denom = sqrt(vi) / ad.bc2_sqrt + ad.eps;
-        const double pn = pp - ad.step_size * (mi / denom);
-        ad.m[p] = mi;
-        ad.v[p] = vi;
+    if (MODE == DW_ADAM) {   // on the parameters this tile owns
+        const double pn = adam_update(ad.s, gsum, pm, pv, pp);
+        ad.m[p] = pm;
+        ad.v[p] = pv;
         ad.params[p] = pn;
         if (ad.pcopy) ad.pcopy[p] = pn;
         if (sc0 >= 0) ad.packed[sc0] = pn;
@@ -1115,9 +1111,7 @@ int fused64_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const do
     ad.packed = (double *)st->packed.p;
     ad.sc_off = (const int *)st->sc_off.p; ad.sc_idx = (const int *)st->sc_idx.p;
     ad.loss_accum = loss_accum;
-    ad.b1 = hp->beta1; ad.b2 = hp->beta2; ad.eps = hp->eps;      // same scalars as launch_adam (elementwise.hip)
-    ad.step_size = hp->lr / (1.0 - pow(hp->beta1, (double)hp->step));
-    ad.bc2_sqrt = sqrt(1.0 - pow(hp->beta2, (double)hp->step));
+    ad.s = adam_scalars(*hp);
     return st->ops->step(h, st, x, x_dtype, n, features, (double *)grads, &ad, s);
 }
 

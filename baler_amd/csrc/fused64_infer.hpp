@@ -169,19 +169,9 @@ __global__ void __launch_bounds__(256) infer64_kernel(const d4 *packed, const vo
         iseq_tail<SQ, SQ::real>(ring, ws, std::make_integer_sequence<int, SQ::total - SQ::real>{});      // step over the padding
     }
     if constexpr (KIND == I_FORWARD) {      // per-workgroup loss partial, fixed order
-        red[threadIdx.x] = lacc;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) loss_part[blockIdx.x] = red[0];
+        const double wsum = block_sum_tree(lacc, red);
+        if (threadIdx.x == 0) loss_part[blockIdx.x] = wsum;
     }
-}
-__global__ void __launch_bounds__(256) sum_loss64_k(const double *__restrict__ part, int n, double scale, double *__restrict__ out) {
-    __shared__ double sh[256];
-    const double s = block_sum_fixed(part, n, sh);
-    if (threadIdx.x == 0) *out = s * scale;
 }
 
 // The launch of one shape (what Impl64::infer was): persistent grid, two workgroups per CU, the loss partials summed by a second launch
@@ -208,7 +198,7 @@ int infer64_run(bamd_handle *h, const double *packed, int kind, const void *x, i
     else {
         hipLaunchKernelGGL((infer64_kernel<F, Z, I_FORWARD, RT>), dim3(grid), dim3(256), lds, s, (const d4 *)packed, x, in64, n, features,
                            out, out64, renorm, imask, (double *)h->lossp.p, fr, zr);
-        hipLaunchKernelGGL(sum_loss64_k, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, grid, 1.0 / fr, loss_sum);
+        hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, grid, 1.0 / fr, loss_sum, 0);
     }
     BAMD_HIP(hipGetLastError());
     return BAMD_OK;

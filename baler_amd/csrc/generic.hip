@@ -112,13 +112,8 @@ __device__ __forceinline__ void epilogue(const Epi<T> &e, int64_t row, int64_t c
 // fixed-order workgroup sum of the per-thread loss terms -> one partial per workgroup (row-major over the grid)
 __device__ __forceinline__ void block_loss(double lsum, double *__restrict__ part) {
     __shared__ double lsh[256];
-    lsh[threadIdx.x] = lsum;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) lsh[threadIdx.x] += lsh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = lsh[0];
+    const double wsum = block_sum_tree(lsum, lsh);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = wsum;
 }
 
 template <typename T, int EPI, bool A_KFAST, bool B_KFAST>
@@ -327,32 +322,8 @@ __global__ void __launch_bounds__(256) loss_grad_k(const T *__restrict__ r, cons
         if (dz) dz[i] = (T)(2.0 * (double)d * inv_c);
     }
     __shared__ double sh[256];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
-}
-
-template <typename TO>
-__global__ void __launch_bounds__(256) loss_final_k(const double *__restrict__ part, int n, double scale, TO *dst,
-                                                    int accumulate) {
-    // fixed-order tree over <= 1024 partials (one block)
-    __shared__ double sh[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        s = sh[0] * scale;
-        *dst = accumulate ? (TO)((double)*dst + s) : (TO)s;
-    }
+    const double wsum = block_sum_tree(acc, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = wsum;
 }
 
 template <typename T>
@@ -374,13 +345,8 @@ __global__ void __launch_bounds__(256) colmean_k(const T *__restrict__ y, int64_
     double acc = 0.0;
     for (int64_t r = threadIdx.x; r < n; r += blockDim.x) acc += (double)y[r * c + col];
     __shared__ double sh[256];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[col] = sh[0] / (double)n;
+    const double wsum = block_sum_tree(acc, sh);
+    if (threadIdx.x == 0) out[col] = wsum / (double)n;
 }
 
 __global__ void fill_nan_k(double *p, int n) {
@@ -1229,7 +1195,7 @@ static int forward_loss_T(bamd_handle *h, const void *x, int x_dtype, int64_t n,
         int nblk = (int)((count + 255) / 256 < 1024 ? (count + 255) / 256 : 1024);
         hipLaunchKernelGGL(loss_grad_k<T>, dim3(nblk), dim3(256), 0, s, wk.y[h->L], wk.x0, count, 1.0 / c,
                            (T *)nullptr, (double *)h->lossp.p);
-        hipLaunchKernelGGL(loss_final_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, nblk,
+        hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, nblk,
                            1.0 / c, loss_sum, chunk_i > 0 ? 1 : 0);
         if (recon) {
             rc = launch_convert(wk.y[h->L], td, (char *)recon + (size_t)r0 * c * oes, recon_dtype, count, s);
@@ -1354,18 +1320,17 @@ template <typename T> struct SmallDwPlan {
     int64_t w_off[8], b_off[8];
     int L;
 };
-// `ad.on`: the optimiser step of exactly these parameters in the same launch (elementwise.hip adam_k's arithmetic, operation for
-// operation: bamd_train_step == bamd_fwd_bwd + bamd_adam_step to the last bit), the refresh of their packed copies included
+// `ad.on`: the optimiser step of exactly these parameters in the same launch, the refresh of their packed copies included
 template <typename T> struct SmallAdamT {
     T *p, *pcopy, *m, *v, *packed;
     const int *sc_off, *sc_idx;
     double *loss_accum;
-    double b1, b2, eps, step_size, bc2_sqrt;
+    AdamScalars s;
     int64_t np;
     int on;
 };
 using SmallAdam = SmallAdamT<float>;
-// The LAST workgroup is loss_final_k: the fixed-order sum of the forward launch's loss partials -> grads[np] (and the caller's running
+// The LAST workgroup is sum_partials_fixed_k: the fixed-order sum of the forward launch's loss partials -> grads[np] (and the caller's running
 // loss when the optimiser step rides along): one launch fewer per step.
 template <typename T>
 __global__ void __launch_bounds__(256) dw_small_all_k(SmallDwPlan<T> pl, int64_t rows, T *__restrict__ grads, int accumulate, SmallAdamT<T> ad,
@@ -1373,16 +1338,8 @@ __global__ void __launch_bounds__(256) dw_small_all_k(SmallDwPlan<T> pl, int64_t
     using v4 = typename MF<T>::v4;
     if (blockIdx.x == gridDim.x - 1) {
         __shared__ double sh[256];
-        double s = 0.0;
-        for (int k = threadIdx.x; k < nloss; k += 256) s += loss_part[k];
-        sh[threadIdx.x] = s;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-            __syncthreads();
-        }
+        const double s = block_sum_fixed(loss_part, nloss, sh) * loss_scale;
         if (threadIdx.x == 0) {
-            s = sh[0] * loss_scale;
             const T lv = accumulate ? (T)((double)grads[np] + s) : (T)s;
             grads[np] = lv;
             if (ad.on && ad.loss_accum) *ad.loss_accum += (double)lv;
@@ -1445,17 +1402,12 @@ __global__ void __launch_bounds__(256) dw_small_all_k(SmallDwPlan<T> pl, int64_t
         if (pidx[r] < 0) continue;
         grads[pidx[r]] = gv[r];
         if (ad.on) {
-            const double gi = (double)gv[r];
-            double mi = (double)pm[r], vi = (double)pv[r];
-            mi = mi + (gi - mi) * (1.0 - ad.b1);
-            vi = vi * ad.b2 + (1.0 - ad.b2) * gi * gi;
-            const double denom = sqrt(vi) / ad.bc2_sqrt + ad.eps;
-            const double pn = (double)pp[r] - ad.step_size * (mi / denom);
-            ad.m[pidx[r]] = (T)mi;
-            ad.v[pidx[r]] = (T)vi;
-            ad.p[pidx[r]] = (T)pn;
-            if (ad.pcopy) ad.pcopy[pidx[r]] = (T)pn;
-            for (int k = so0[r]; k < so1[r]; ++k) ad.packed[ad.sc_idx[k]] = (T)pn;
+            const T pn = adam_update(ad.s, gv[r], pm[r], pv[r], pp[r]);
+            ad.m[pidx[r]] = pm[r];
+            ad.v[pidx[r]] = pv[r];
+            ad.p[pidx[r]] = pn;
+            if (ad.pcopy) ad.pcopy[pidx[r]] = pn;
+            for (int k = so0[r]; k < so1[r]; ++k) ad.packed[ad.sc_idx[k]] = pn;
         }
     }
 }
@@ -1561,7 +1513,7 @@ static int fwd_bwd_T(bamd_handle *h, const void *x, int x_dtype, int64_t n, cons
         const bool dw_small = route.dw_small;      // every weight gradient in ONE launch, behind the input-gradient chain
         if (adam && !dw_small) { set_error("fwd_bwd_T: optimiser step asked of a chunk that is not on dw_small_all_k"); return BAMD_ERR_UNSUPPORTED; }
         if (!dw_small)      // (that launch also sums the loss partials)
-            hipLaunchKernelGGL(loss_final_k<T>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, nblk, 1.0 / c,
+            hipLaunchKernelGGL(sum_partials_fixed_k<T>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, nblk, 1.0 / c,
                                grads + np, chunk_i > 0 ? 1 : 0);
         if (wide) {
             rc = fused_wide_train_backward(h, rows, (float *const *)wk.y.data(), (float *const *)wk.dz.data(),
@@ -1650,9 +1602,7 @@ int generic_small_train_step(bamd_handle *h, const void *x, int x_dtype, int64_t
     fused_scatter(h, &sa.sc_off, &sa.sc_idx, &packed);
     sa.packed = (float *)packed;
     sa.loss_accum = loss_accum;
-    sa.b1 = hp.beta1; sa.b2 = hp.beta2; sa.eps = hp.eps;                    // the scalars of launch_adam (elementwise.hip)
-    sa.step_size = hp.lr / (1.0 - pow(hp.beta1, (double)hp.step));
-    sa.bc2_sqrt = sqrt(1.0 - pow(hp.beta2, (double)hp.step));
+    sa.s = adam_scalars(hp);
     sa.np = h->nparams;
     sa.on = 1;
     return fwd_bwd_T<float>(h, x, x_dtype, n, features, grads, nullptr, s, &sa);

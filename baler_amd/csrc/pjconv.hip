@@ -312,13 +312,8 @@ __global__ void __launch_bounds__(256) dec5_k(Dec5Args a) {
         }
     }
     if (!a.loss_part) return;
-    sh[threadIdx.x] = l;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.loss_part[blockIdx.x] = sh[0];
+    const double wsum = block_sum_tree(l, sh);
+    if (threadIdx.x == 0) a.loss_part[blockIdx.x] = wsum;
 }
 
 __global__ void __launch_bounds__(256) loss_final_k(const double *part, int n, float *gloss, double *loss_sum) {

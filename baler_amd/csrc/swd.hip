@@ -68,13 +68,8 @@ __global__ void __launch_bounds__(256) swd_sort_k(const T *__restrict__ z, const
         acc += (double)w * (double)w;
         G[(int64_t)s * n + ai[i]] = (T)(2.0 * scale) * w;
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] += red[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) part[s] = red[0];
+    const double wsum = block_sum_tree(acc, red);
+    if (tid == 0) part[s] = wsum;
 }
 
 // ---- batches that do not fit one workgroup's LDS (n > 4096): the same bitonic network in passes through global memory --------
@@ -154,13 +149,8 @@ __global__ void __launch_bounds__(256) swd_finish_k(const T *__restrict__ AV, co
         acc += (double)w * (double)w;
         G[(int64_t)s * n + AI[base + i]] = (T)(2.0 * scale) * w;
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] += red[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) part[s] = red[0];
+    const double wsum = block_sum_tree(acc, red);
+    if (tid == 0) part[s] = wsum;
 }
 
 template <typename T>
@@ -174,11 +164,6 @@ __global__ void __launch_bounds__(256) swd_dz_k(const T *__restrict__ G, const T
     dz[(int64_t)row * d + k] = acc;
 }
 
-__global__ void __launch_bounds__(256) swd_loss_k(const double *__restrict__ part, int ns, double scale, double *__restrict__ out) {
-    __shared__ double sh[256];
-    const double s = block_sum_fixed(part, ns, sh);
-    if (threadIdx.x == 0) *out = s * scale;
-}
 
 template <typename T>
 int swd_T(const void *z, const void *prior, const void *proj, int n, int d, int ns, double reg_weight, double *loss_out,
@@ -218,7 +203,7 @@ int swd_T(const void *z, const void *prior, const void *proj, int n, int d, int 
     }
     hipLaunchKernelGGL(swd_dz_k<T>, dim3((unsigned)(((int64_t)n * d + 255) / 256)), dim3(256), 0, s, (const T *)G,
                        (const T *)proj, n, d, ns, (T *)dz_out);
-    hipLaunchKernelGGL(swd_loss_k, dim3(1), dim3(256), 0, s, (const double *)part, ns, scale, loss_out);
+    hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)part, ns, scale, loss_out, 0);
     BAMD_HIP(hipGetLastError());
     return BAMD_OK;
 }
