@@ -1,6 +1,6 @@
 """CLI driver (mirror of ``baler/baler.py`` for the train / compress / decompress / info modes).
 
-``python -m baler_amd --project WORKSPACE PROJECT --mode {newProject,train,compress,decompress,info}``
+``python -m baler_amd --project WORKSPACE PROJECT --mode {newProject,train,compress,decompress,report,info}``
 works on an unmodified reference-style workspace tree and writes byte-compatible artefacts
 (model.pt, compressed.npz, decompressed.npz, loss_data.npy, normalization_features.npy,
 activations.npy), so the reference's plot / diagnose modes can consume them.
@@ -17,7 +17,7 @@ import torch
 from . import dist as bdist
 from .modules import helper
 
-__all__ = ("perform_compression", "perform_decompression", "perform_training", "print_info")
+__all__ = ("perform_compression", "perform_decompression", "perform_training", "perform_report", "print_info")
 
 
 def main(argv=None):
@@ -33,11 +33,14 @@ def main(argv=None):
         perform_compression(output_path, config, verbose)
     elif mode == "decompress":
         perform_decompression(output_path, config, verbose)
+    elif mode == "report":
+        perform_report(output_path, config, verbose)
     elif mode == "info":
         print_info(output_path, config)
     elif mode in ("plot", "diagnose", "convert_with_hls4ml"):
         raise NameError(f"Baler mode {mode} consumes artefacts only; run it with the reference CLI on the "
-                        "outputs written by baler_amd (the artefact formats are identical).")
+                        "outputs written by baler_amd (the artefact formats are identical).  The per-column statistics "
+                        "and histograms behind plot's comparison pages are computed here by --mode report.")
     else:
         raise NameError("Baler mode " + mode + " not recognised. Use baler_amd --help to see available modes.")
     bdist.barrier()      # rank 0 writes the artefacts: no rank leaves a mode before they are complete
@@ -185,6 +188,15 @@ def perform_decompression(output_path, config, verbose: bool):
     print("Decompression took:", f"{(end - start) / 60:.3} minutes")
     saver = np.savez_compressed if config.extra_compression else np.savez
     saver(os.path.join(output_path, "decompressed_output", "decompressed.npz"), data=decompressed, names=names)
+
+
+def perform_report(output_path, config, verbose: bool):
+    """The numbers behind the reference's plot mode for 1-D data (plotting.plot_1D, plotting.py:101-239) -> output/plotting/column_stats.npz."""
+    helper.check_report(config)        # before any GPU work
+    start = time.time()
+    helper.column_report(config, output_path, verbose)
+    if bdist.rank_world()[0] == 0:
+        print("Report took:", f"{(time.time() - start) / 60:.3} minutes")
 
 
 def print_info(output_path, config):

@@ -34,7 +34,7 @@ def get_arguments(argv=None):
         description="MI355X-native train/compress/decompress path of Baler (same CLI as `baler`).",
         formatter_class=argparse.RawTextHelpFormatter)
     parser.add_argument("--mode", type=str, required=True,
-                        help="newProject, train, compress, decompress, info")
+                        help="newProject, train, compress, decompress, report, info")
     parser.add_argument("--project", type=str, required=True, nargs=2, metavar=("WORKSPACE", "PROJECT"),
                         help="Specifies workspace and project, e.g. --project CMS_workspace CMS_project_v1")
     parser.add_argument("--verbose", dest="verbose", action="store_true", help="Verbose mode")
@@ -544,3 +544,119 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
         else:
             decompressed = decompressed.reshape((len(decompressed), original_shape[1], original_shape[2]))
     return decompressed, names, normalization_features
+
+
+# ---- --mode report: the data path of plotting.plot_1D ----------------------------------------------------------------------------
+REPORT_CUT = (3, 1e-6)      # plotting.py:118: get_index_to_cut(3, 1e-6, before), hard-coded in the reference
+
+
+def report_response_edges():
+    return np.arange(-20, 20, 0.1)          # plotting.py:194
+
+
+def report_residual_edges():
+    return np.arange(-1, 1, 0.01)           # plotting.py:217
+
+
+def report_value_edges(x_min, x_max):
+    """plotting.py:146-153 with x_min / x_max = the extrema of before + after of one column (scalars of the table's dtype)."""
+    x_diff = abs(x_max - x_min)
+    return np.linspace(x_min - 0.1 * x_diff, x_max + 0.1 * x_diff, 200)
+
+
+def report_cut(config, n_cols):
+    """The row cut of the report: config.report_cut = (column, value) or None when the config sets it; else the reference's
+    (3, 1e-6) for tables of more than 3 columns (the reference indexes column 3 unconditionally) and no cut for narrower ones."""
+    if hasattr(config, "report_cut"):
+        cut = config.report_cut
+        if cut is None:
+            return None
+        col, value = int(cut[0]), float(cut[1])
+        if not 0 <= col < n_cols:
+            raise ValueError(f"report_cut column {col} is outside the table's {n_cols} columns")
+        return col, value
+    return REPORT_CUT if n_cols > 3 else None
+
+
+def report_chunk_rows(config, row_bytes):
+    """Rows per device chunk of the report: config.report_chunk_rows, else what fills one of hostio's staging buffers."""
+    rows = getattr(config, "report_chunk_rows", None)
+    return max(1, int(rows)) if rows else max(1, hostio.CHUNK_BYTES // max(1, row_bytes))
+
+
+def check_report(config):
+    if config.data_dimension != 1:
+        raise NotImplementedError("--mode report serves data_dimension = 1 (plotting.plot_1D); plotting.plot_2D has no native "
+                                  "path: run the reference's plot mode on the artefacts")
+
+
+def column_report(config, output_path, verbose=False):
+    """The data path of plotting.plot_1D (plotting.py:101-239) on the device: per column the mean / RMS of the residual
+    after - before and of the response (after - before) / before * 100, the residual's extrema, and the response, residual,
+    before and after histograms with the reference's bins.  Both tables stream through the GPU in row chunks, twice: moments,
+    then -- the value bins come from the before + after extrema -- histograms; the tables never have to fit on the device.
+    Under data parallelism each rank takes a contiguous row slice; sums and counts are SUM-, extrema MIN- / MAX-all-reduced.
+    Returns the dict that rank 0 also writes to output/plotting/column_stats.npz."""
+    check_report(config)
+    device = get_device()
+    rank, world = bdist.rank_world()
+    before = hostio.open_npz_array(config.input_path, "data")
+    after = hostio.open_npz_array(os.path.join(output_path, "decompressed_output", "decompressed.npz"), "data")
+    names = np.load(config.input_path)["names"]
+    if before.ndim != 2 or before.shape != after.shape:
+        raise ValueError(f"report: input {before.shape} and decompressed {after.shape} must be two tables of one shape")
+    n, c = before.shape
+    cut = report_cut(config, c)
+    t_dtype, h_dtype = hostio._device_dtype(np.result_type(before.dtype, after.dtype))
+    lo, hi = bdist.shard_rows(n, rank, world)
+    chunk = report_chunk_rows(config, 2 * c * np.dtype(h_dtype).itemsize)
+
+    def chunks():
+        for a in range(lo, hi, chunk):
+            plan = hostio.RowPlan("range", n, lo=a, hi=min(a + chunk, hi), count=min(a + chunk, hi) - a)
+            b_dev, a_dev = hostio.upload_rows(before, plan, device), hostio.upload_rows(after, plan, device)
+            yield b_dev.to(t_dtype), a_dev.to(t_dtype)      # (a no-op unless the two archives differ in dtype)
+
+    # sweep 1: moments
+    empty = torch.empty((0, c), dtype=t_dtype, device=device)
+    raw = native.column_moments_raw(empty, empty, cut)           # the neutral elements (a rank may own no rows)
+    for b_dev, a_dev in chunks():
+        native.column_moments_raw(b_dev, a_dev, cut, out=raw)
+    if world > 1:
+        import torch.distributed as td
+        for rows, op in ((native.MOMENT_SUM_ROWS, td.ReduceOp.SUM), (native.MOMENT_MIN_ROWS, td.ReduceOp.MIN),
+                         (native.MOMENT_MAX_ROWS, td.ReduceOp.MAX)):
+            part = raw[list(rows)].contiguous()
+            td.all_reduce(part, op=op)
+            raw[list(rows)] = part
+    stats = native.moments_summary(raw)
+
+    # the reference's bins, built by the very numpy calls it uses
+    e_resp, e_resid = report_response_edges(), report_residual_edges()
+    with np.errstate(invalid="ignore"):      # a column without kept values: NaN edges, nothing is counted
+        e_val = np.stack([np.asarray(report_value_edges(h_dtype(stats["sum_min"][k]), h_dtype(stats["sum_max"][k])), dtype=np.float64)
+                          for k in range(c)])
+    dev = lambda x: torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).to(device)   # noqa: E731
+    d_resp, d_resid, d_val = dev(e_resp), dev(e_resid), dev(e_val)
+
+    # sweep 2: histograms
+    counts = native.column_hist(empty, empty, d_resp, d_resid, d_val, cut)    # zeros
+    for b_dev, a_dev in chunks():
+        native.column_hist(b_dev, a_dev, d_resp, d_resid, d_val, cut, out=counts)
+    if world > 1:
+        for t in counts.values():
+            bdist.allreduce_sum(t)
+    result = {"names": names, "cut": np.array(cut if cut is not None else (-1, 0.0), dtype=np.float64)}
+    result.update(stats)
+    result.update(edges_response=e_resp, edges_residual=e_resid, edges_value=e_val,
+                  counts_response=counts["resp"].cpu().numpy(), counts_residual=counts["resid"].cpu().numpy(),
+                  counts_before=counts["before"].cpu().numpy(), counts_after=counts["after"].cpu().numpy())
+    if rank == 0:
+        os.makedirs(os.path.join(output_path, "plotting"), exist_ok=True)
+        np.savez(os.path.join(output_path, "plotting", "column_stats.npz"), **result)
+        print("=== Column report ===")
+        for k in range(c):
+            print(f"{str(names[k]).split('.')[-1]}: residual mean {stats['resid_mean'][k]:.6g} RMS {stats['resid_rms'][k]:.6g} "
+                  f"min {stats['resid_min'][k]:.6g} max {stats['resid_max'][k]:.6g}; response mean {stats['resp_mean'][k]:.4g} % "
+                  f"RMS {stats['resp_rms'][k]:.4g} %")
+    return result

@@ -28,6 +28,7 @@ SYMBOLS = (
     "bamd_error_deltas", "bamd_apply_deltas", "bamd_fwd_bwd_latent", "bamd_swd", "bamd_col_minmax", "bamd_path_of",
     "bamd_train_epoch", "bamd_comm_unique_id", "bamd_comm_init", "bamd_comm_attach", "bamd_comm_release", "bamd_comm_world",
     "bamd_allreduce_sum", "bamd_train_epoch_dp", "bamd_create_act", "bamd_act_of", "bamd_create_pjconv",
+    "bamd_column_moments", "bamd_column_hist",
 )
 PJ_FEATURES = 784      # PJ_Conv_AE: one 28 x 28 frame per row
 
@@ -97,6 +98,8 @@ def lib():
     L.bamd_fwd_bwd_latent.argtypes = [vp, vp, ci, i64, vp, vp, vp, vp]
     L.bamd_swd.argtypes = [vp, vp, vp, ci, i64, ci, ci, dbl, vp, vp, vp]
     L.bamd_apply_deltas.argtypes = [vp, ci, ci, vp, vp, vp, i64, vp]
+    L.bamd_column_moments.argtypes = [vp, vp, ci, i64, ci, ci, dbl, vp, ci, vp]
+    L.bamd_column_hist.argtypes = [vp, vp, ci, i64, ci, ci, dbl, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp]
     for name in SYMBOLS:
         getattr(L, name)
     _lib = L
@@ -256,6 +259,101 @@ def apply_deltas(out, rows, cols, deltas):
         _check(lib().bamd_apply_deltas(_ptr(out), _dt(out), out.shape[1], _ptr(rows), _ptr(cols), _ptr(deltas),
                                        rows.numel(), _stream(out)), "bamd_apply_deltas")
     return out
+
+
+# rows of bamd_column_moments' (13, n_cols) output (include/baler_amd.h)
+MOMENT_ROWS = ("count", "resid_sum", "resid_sumsq", "resid_min", "resid_max", "resp_sum", "resp_sumsq",
+               "before_min", "before_max", "after_min", "after_max", "sum_min", "sum_max")
+MOMENT_SUM_ROWS, MOMENT_MIN_ROWS, MOMENT_MAX_ROWS = (0, 1, 2, 5, 6), (3, 7, 9, 11), (4, 8, 10, 12)
+
+
+def _table_pair(what, before, after):
+    before, after = _dev_tensor(before), _dev_tensor(after)
+    if before.dtype != after.dtype or before.shape != after.shape or before.dim() != 2:
+        raise NativeError(f"{what}: before and after must be two (n, c) tables of one dtype and shape")
+    _same_device(what, before, after)
+    return before, after
+
+
+def _cut_args(cut):
+    """cut = (column, value) or None -> the (cut_col, cut) pair of the C ABI."""
+    return (-1, 0.0) if cut is None else (int(cut[0]), float(cut[1]))
+
+
+def moments_summary(raw):
+    """The (13, c) sums / extrema of bamd_column_moments (tensor or array) -> dict of float64 numpy arrays of length c: count,
+    resid_mean, resid_rms, resid_min, resid_max, resp_mean, resp_rms, before_min, ..., sum_max (plotting.py:143-147, 203-234:
+    mean = sum / count, RMS = sqrt(sum of squares / count))."""
+    import numpy as np
+    r = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    d = dict(zip(MOMENT_ROWS, r))
+    with np.errstate(all="ignore"):
+        out = {"count": d["count"].astype(np.int64),
+               "resid_mean": d["resid_sum"] / d["count"], "resid_rms": np.sqrt(d["resid_sumsq"] / d["count"]),
+               "resid_min": d["resid_min"], "resid_max": d["resid_max"],
+               "resp_mean": d["resp_sum"] / d["count"], "resp_rms": np.sqrt(d["resp_sumsq"] / d["count"])}
+    for k in MOMENT_ROWS[7:]:
+        out[k] = d[k]
+    return out
+
+
+def column_moments_raw(before, after, cut=None, out=None):
+    """bamd_column_moments: -> the (13, c) float64 device tensor of sums and extrema (rows: MOMENT_ROWS).  With ``out`` (the
+    result of an earlier call) this call's rows are ADDED to it: a table can be fed in row chunks."""
+    before, after = _table_pair("column_moments", before, after)
+    n, c = before.shape
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty((13, c), dtype=torch.float64, device=before.device)
+    elif tuple(out.shape) != (13, c) or out.dtype != torch.float64:
+        raise NativeError("column_moments: out must be a (13, n_cols) float64 tensor")
+    _same_device("column_moments", before, _dev_tensor(out))
+    cut_col, cut_val = _cut_args(cut)
+    with torch.cuda.device(before.device):
+        _check(lib().bamd_column_moments(_ptr(before), _ptr(after), _dt(before), n, c, cut_col, cut_val, _ptr(out),
+                                         int(accumulate), _stream(before)), "bamd_column_moments")
+    return out
+
+
+def column_moments(before, after, cut=None, out=None):
+    """Per-column residual / response statistics of plotting.plot_1D (see moments_summary) of two device tables; cut = (column,
+    value) drops the rows with before[:, column] < value.  ``out``: as in column_moments_raw (the summary is then of all rows so far)."""
+    return moments_summary(column_moments_raw(before, after, cut, out))
+
+
+def column_hist(before, after, edges_resp=None, edges_resid=None, edges_val=None, cut=None, out=None):
+    """bamd_column_hist: np.histogram with explicit bins of the response, the residual, ``before`` and ``after`` of every column.
+    edges_resp (n_er,), edges_resid (n_ed,), edges_val (c, n_ev): float64 device tensors, or None to skip that histogram.
+    -> dict of int64 device tensors "resp" (c, n_er - 1), "resid" (c, n_ed - 1), "before" and "after" (c, n_ev - 1) for the
+    histograms asked for.  ``out`` (such a dict from an earlier call): the counts of this call's rows are added to it."""
+    before, after = _table_pair("column_hist", before, after)
+    n, c = before.shape
+    accumulate = out is not None
+    res = dict(out) if accumulate else {}
+    ptr, cnt = {}, {}
+    for key, e, names in (("resp", edges_resp, ("resp",)), ("resid", edges_resid, ("resid",)), ("val", edges_val, ("before", "after"))):
+        if e is None:
+            ptr[key], cnt[key] = None, 0
+            continue
+        e = _dev_tensor(e)
+        want_dim = 2 if key == "val" else 1
+        if e.dtype != torch.float64 or e.dim() != want_dim or (key == "val" and e.shape[0] != c):
+            raise NativeError(f"column_hist: edges_{key} must be float64 of shape " + ("(n_cols, n_edges)" if key == "val" else "(n_edges,)"))
+        _same_device("column_hist", before, e)
+        ptr[key], cnt[key] = e, int(e.shape[-1])
+        for nm in names:
+            if not accumulate:
+                res[nm] = torch.empty((c, max(cnt[key] - 1, 0)), dtype=torch.int64, device=before.device)
+            elif nm not in res or tuple(res[nm].shape) != (c, cnt[key] - 1) or res[nm].dtype != torch.int64:
+                raise NativeError(f"column_hist: out[{nm!r}] must be an int64 tensor of shape (n_cols, n_edges - 1)")
+    cut_col, cut_val = _cut_args(cut)
+    with torch.cuda.device(before.device):
+        _check(lib().bamd_column_hist(_ptr(before), _ptr(after), _dt(before), n, c, cut_col, cut_val,
+                                      _ptr(ptr["resp"]), cnt["resp"], _ptr(res.get("resp")),
+                                      _ptr(ptr["resid"]), cnt["resid"], _ptr(res.get("resid")),
+                                      _ptr(ptr["val"]), cnt["val"], _ptr(res.get("before")), _ptr(res.get("after")),
+                                      int(accumulate), _stream(before)), "bamd_column_hist")
+    return res
 
 
 # ---- model handle ---------------------------------------------------------------------------------

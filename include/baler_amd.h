@@ -321,6 +321,35 @@ int bamd_apply_deltas(void *out, int dtype, int n_cols, const int64_t *rows, con
  * device memory, padded with NaN. */
 int bamd_activation_means(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows,
                           const double *features, double *out, int max_nodes, void *stream);
+/* Replaces: the per-column statistics of plotting.plot_1D (plotting.py:118-123, 143-147, 203-234) -- residual = after - before,
+ * response = (after - before) / before * 100, their mean and RMS, the residual's extrema and the value range -- for two row-major
+ * tables before / after (n_rows, n_cols), both of `dtype`; n_cols 1 .. 128 (more: BAMD_ERR_UNSUPPORTED).  Handle-free.
+ * Row cut (plotting.get_index_to_cut, plotting.py:60-73, 118-120): a row is left out of every statistic when
+ * before[row][cut_col] < cut; a NaN there keeps the row, as numpy's comparison does; cut_col < 0: no cut.
+ * The elementwise arithmetic is numpy's: the input dtype, one rounding per operation (fp32 division correctly rounded).
+ * out: (13, n_cols) float64, device memory, one row per statistic over the kept rows of each column:
+ *    0 count            1 sum(residual)   2 sum(residual^2)   3 min(residual)   4 max(residual)
+ *    5 sum(response)    6 sum(response^2)
+ *    7 min(before)      8 max(before)     9 min(after)       10 max(after)
+ *   11 min(before + after)               12 max(before + after)      (plot_1D's histogram range, plotting.py:146-147)
+ * Sums are float64 whatever the dtype, in a fixed order (no float atomics: bitwise repeatable), and propagate inf / NaN as IEEE
+ * does (a zero in `before` gives +-inf or NaN, as in numpy); extrema skip NaN; a column without kept values has +inf / -inf.
+ * accumulate != 0: `out` holds the result of earlier calls and this call's rows are added to it (sums and the count add, extrema
+ * combine), so a table can be fed in row chunks.  n_rows = 0: BAMD_OK; `out` is set to the neutral elements, or left alone. */
+int bamd_column_moments(const void *before, const void *after, int dtype, int64_t n_rows, int n_cols, int cut_col, double cut,
+                        double *out, int accumulate, void *stream);
+/* Replaces: the four np.histogram calls per column of plotting.plot_1D (plotting.py:150-170, 192-224): response, residual, before
+ * and after, with the tables, the row cut and the arithmetic of bamd_column_moments.  Edge arrays are float64 device memory,
+ * strictly increasing, 2 .. 1025 edges each: edges_resp[n_er] and edges_resid[n_ed] serve every column, edges_val is
+ * (n_cols, n_ev) and serves `before` and `after` of its column; a NULL edge array skips that histogram.  counts_* are int64
+ * device memory, (n_cols, edges - 1).  numpy's rule for explicit bins: bin k holds edges[k] <= v < edges[k+1], the last bin also
+ * v == edges[-1]; NaN and values outside [edges[0], edges[-1]] are not counted; values are compared as float64.
+ * accumulate != 0: the counts of this call's rows are added to counts_*; otherwise they are overwritten.  Integer sums: the
+ * result does not depend on any order.  n_rows = 0: BAMD_OK (counts zeroed, or left alone). */
+int bamd_column_hist(const void *before, const void *after, int dtype, int64_t n_rows, int n_cols, int cut_col, double cut,
+                     const double *edges_resp, int n_er, int64_t *counts_resp, const double *edges_resid, int n_ed,
+                     int64_t *counts_resid, const double *edges_val, int n_ev, int64_t *counts_before, int64_t *counts_after,
+                     int accumulate, void *stream);
 
 #ifdef __cplusplus
 }
