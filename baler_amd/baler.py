@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import dist as bdist
+from . import hostio
 from .modules import helper
 
 __all__ = ("perform_compression", "perform_decompression", "perform_training", "perform_report", "print_info")
@@ -119,6 +120,7 @@ def perform_training(output_path, config, verbose: bool):
 
 def perform_compression(output_path, config, verbose: bool):
     """reference baler.py:239-338."""
+    helper.latent_dtype_of(config)      # a bad config.latent_dtype fails before any GPU work
     if helper.is_convolutional(config):
         helper.check_convolutional(config)
     print("Compressing...")
@@ -136,8 +138,10 @@ def perform_compression(output_path, config, verbose: bool):
         return
     names = np.load(config.input_path)["names"]
     saver = np.savez_compressed if config.extra_compression else np.savez
-    saver(os.path.join(output_path, "compressed_output", "compressed.npz"), data=compressed, names=names,
-          normalization_features=normalization_features)
+    # config.latent_dtype: float16 codes are a float16 `data`; bfloat16 codes are uint16 bit patterns + the key latent_dtype
+    fields = hostio.latent_to_archive(compressed, helper.latent_dtype_of(config))
+    saver(os.path.join(output_path, "compressed_output", "compressed.npz"), data=fields.pop("data"), names=names,
+          normalization_features=normalization_features, **fields)
     if getattr(config, "save_error_bounded_deltas", False):    # baler.py:316-338
         helper.save_deltas(os.path.join(output_path, "compressed_output"), error_bound_batch, error_bound_deltas,
                            error_bound_index)

@@ -52,6 +52,11 @@ struct DeviceGuard {
 };
 }  // namespace
 
+// BAMD_F16 / BAMD_BF16 are storage types of latent codes: legal as z_dtype of bamd_encode / bamd_decode and nowhere else.  Every other
+// dtype argument is checked here, by name, before anything is launched or written.
+#define BAMD_WIDE_DTYPE(d, name) \
+    BAMD_REQUIRE(dtype_wide(d), name " must be BAMD_F32 or BAMD_F64 (BAMD_F16 / BAMD_BF16 are latent codes: z_dtype of bamd_encode / bamd_decode only)")
+
 extern "C" {
 
 int bamd_abi_version(void) { return BAMD_ABI_VERSION; }
@@ -229,6 +234,7 @@ void bamd_destroy(bamd_handle *h) {
     h->slabs.release();
     h->lossp.release();
     h->gscratch.release();
+    h->lat32.release();
     delete h;
 }
 
@@ -238,7 +244,7 @@ int bamd_act_of(const bamd_handle *h) { return h ? h->act : BAMD_ERR_INVALID; }
 
 int bamd_load_params(bamd_handle *h, const void *params, int dtype, void *stream) {
     BAMD_REQUIRE(h && params, "null argument");
-    BAMD_REQUIRE(dtype == BAMD_F32 || dtype == BAMD_F64, "bad dtype");
+    BAMD_WIDE_DTYPE(dtype, "dtype");
     DeviceGuard guard(h->device);
     BAMD_REQUIRE(guard.rc == hipSuccess, "cannot select the handle's device");
     hipStream_t s = (hipStream_t)stream;
@@ -258,20 +264,25 @@ int bamd_load_params(bamd_handle *h, const void *params, int dtype, void *stream
 }
 
 int bamd_minmax(const void *x, int dtype, int64_t n_rows, int n_cols, double *features, void *stream) {
+    BAMD_WIDE_DTYPE(dtype, "dtype");
     return launch_minmax(x, dtype, n_rows, n_cols, features, (hipStream_t)stream);
 }
 
 int bamd_col_minmax(const void *x, int dtype, int64_t n_rows, int n_cols, double *minmax, void *stream) {
+    BAMD_WIDE_DTYPE(dtype, "dtype");
     return launch_minmax(x, dtype, n_rows, n_cols, minmax, (hipStream_t)stream, true);
 }
 
 int bamd_normalize(const void *x, int dtype, int64_t n_rows, int n_cols, const double *features, void *out,
                    int out_dtype, void *stream) {
+    BAMD_WIDE_DTYPE(dtype, "dtype");
+    BAMD_WIDE_DTYPE(out_dtype, "out_dtype");
     return launch_normalize(x, dtype, n_rows, n_cols, features, out, out_dtype, (hipStream_t)stream);
 }
 
 int bamd_renormalize(const void *x, int dtype, int64_t n_rows, int n_cols, const double *features,
                      const uint8_t *int_mask, double *out, void *stream) {
+    BAMD_WIDE_DTYPE(dtype, "dtype");
     return launch_renormalize(x, dtype, n_rows, n_cols, features, int_mask, out, (hipStream_t)stream);
 }
 
@@ -315,45 +326,106 @@ static int params_stepped(bamd_handle *h, hipStream_t s) {
     DeviceGuard guard_((h)->device);                                               \
     BAMD_REQUIRE(guard_.rc == hipSuccess, "cannot select the handle's device");
 
-int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features, void *z,
-                int z_dtype, void *stream) {
-    BAMD_CHECK_MODEL(h);
-    BAMD_REQUIRE(n_rows >= 0 && ((x && z) || n_rows == 0), "bad arguments");
-    if (n_rows == 0) return BAMD_OK;
-    hipStream_t s = (hipStream_t)stream;
+// The family dispatch of bamd_encode / bamd_decode.  z_dtype may be a 16-bit type only where latent_in_kernel() says the family's
+// kernels round / widen the codes themselves.
+static int encode_rows(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features, void *z, int z_dtype,
+                       hipStream_t s) {
     if (h->pj_state) return pj_encode(h, x, x_dtype, n_rows, features, z, z_dtype, s);
     if (int rc = bf16_sync(h, s)) return rc;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return bf16_encode(h, x, x_dtype, n_rows, features, z, z_dtype, s);
     if (h->fpga_state) return fpga_infer(h, 0, x, x_dtype, n_rows, features, z, z_dtype, nullptr, nullptr, nullptr, s);
     if (h->fused_ok) return fused_encode(h, x, x_dtype, n_rows, features, z, z_dtype, s);
-    if (h->mode == BAMD_MODE_F64) {
+    if (h->mode == BAMD_MODE_F64 && dtype_wide(z_dtype)) {
         const int rc = fused64_infer(h, 0, x, x_dtype, n_rows, features, z, z_dtype, nullptr, nullptr, nullptr, s);
         if (rc != BAMD_ERR_UNSUPPORTED) return rc;
     }
     return generic_forward(h, x, x_dtype, n_rows, features, 0, h->L / 2, z, z_dtype, nullptr, nullptr, s);
 }
 
-int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, const double *features,
-                const uint8_t *int_mask, void *out, int out_dtype, void *stream) {
-    BAMD_CHECK_MODEL(h);
-    BAMD_REQUIRE(n_rows >= 0 && ((z && out) || n_rows == 0), "bad arguments");
-    if (n_rows == 0) return BAMD_OK;
-    hipStream_t s = (hipStream_t)stream;
+static int decode_rows(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, const double *features, const uint8_t *int_mask,
+                       void *out, int out_dtype, hipStream_t s) {
     if (h->pj_state) return pj_decode(h, z, z_dtype, n_rows, features, int_mask, out, out_dtype, s);
     if (int rc = bf16_sync(h, s)) return rc;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return bf16_decode(h, z, z_dtype, n_rows, features, int_mask, out, out_dtype, s);
     if (h->fpga_state) return fpga_infer(h, 1, z, z_dtype, n_rows, nullptr, out, out_dtype, features, int_mask, nullptr, s);
     if (h->fused_ok) return fused_decode(h, z, z_dtype, n_rows, features, int_mask, out, out_dtype, s);
-    if (h->mode == BAMD_MODE_F64 && (!features || out_dtype == BAMD_F64)) {      // (un-normalised output is float64, as renormalize_k's)
+    if (h->mode == BAMD_MODE_F64 && dtype_wide(z_dtype) && (!features || out_dtype == BAMD_F64)) {      // (un-normalised output is float64, as renormalize_k's)
         const int rc = fused64_infer(h, 1, z, z_dtype, n_rows, nullptr, out, out_dtype, features, int_mask, nullptr, s);
         if (rc != BAMD_ERR_UNSUPPORTED) return rc;
     }
     return generic_forward(h, z, z_dtype, n_rows, nullptr, h->L / 2, h->L, out, out_dtype, features, int_mask, s);
 }
 
+// 16-bit latent codes (BAMD_F16 / BAMD_BF16).  The register-chain kernels of fused.hip, bf16.hip and the layer-wise path convert in
+// the launch that touches the latent anyway (latent_io.hpp).  The wide-layer kernels, the fp64 chain, the FPGA_prototype_model
+// kernels and the PJ_Conv_AE kernels keep their float32 / float64 stores: their latent goes through a float32 workspace and ONE row-conversion
+// launch -- the same rounding (float32 first, then 16 bits) and the same exact widening, so the results are bit-identical either way.
+static bool latent_in_kernel(const bamd_handle *h) {
+    if (h->pj_state || h->fpga_state) return false;
+    if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return true;
+    if (h->fused_ok) return fused_latent_in_kernel(h);      // the register chain; the wide-layer kernels: workspace
+    return !(h->mode == BAMD_MODE_F64 && h->fused64_state);     // else: the layer-wise kernels
+}
+static int64_t lat32_chunk(const bamd_handle *h) {      // rows per workspace chunk: at most 256 MiB of float32 latents
+    const int64_t e = env_ll("BALER_AMD_LAT32_ROWS", 0);       // (tests: several chunks at small sizes)
+    if (e > 0) return e;
+    const int64_t c = ((int64_t)256 << 20) / ((int64_t)h->dims[h->L / 2] * 4);
+    return c < 1024 ? 1024 : c;
+}
+
+int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features, void *z,
+                int z_dtype, void *stream) {
+    BAMD_CHECK_MODEL(h);
+    BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
+    BAMD_REQUIRE(dtype_wide(z_dtype) || dtype_half(z_dtype), "z_dtype must be BAMD_F32, BAMD_F64, BAMD_F16 or BAMD_BF16");
+    BAMD_REQUIRE(n_rows >= 0 && ((x && z) || n_rows == 0), "bad arguments");
+    if (n_rows == 0) return BAMD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype_wide(z_dtype) || latent_in_kernel(h)) return encode_rows(h, x, x_dtype, n_rows, features, z, z_dtype, s);
+    const int zd = h->dims[h->L / 2];
+    const size_t xrow = (size_t)h->dims[0] * dtype_bytes(x_dtype);
+    const int64_t chunk = lat32_chunk(h);
+    for (int64_t r0 = 0; r0 < n_rows; r0 += chunk) {
+        const int64_t rows = n_rows - r0 < chunk ? n_rows - r0 : chunk;
+        int rc = h->lat32.ensure((size_t)rows * zd * sizeof(float));
+        if (rc) return rc;
+        rc = encode_rows(h, (const char *)x + (size_t)r0 * xrow, x_dtype, rows, features, h->lat32.p, BAMD_F32, s);
+        if (rc) return rc;
+        rc = launch_convert(h->lat32.p, BAMD_F32, (char *)z + (size_t)r0 * zd * 2, z_dtype, rows * zd, s);
+        if (rc) return rc;
+    }
+    return BAMD_OK;
+}
+
+int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, const double *features,
+                const uint8_t *int_mask, void *out, int out_dtype, void *stream) {
+    BAMD_CHECK_MODEL(h);
+    BAMD_REQUIRE(dtype_wide(z_dtype) || dtype_half(z_dtype), "z_dtype must be BAMD_F32, BAMD_F64, BAMD_F16 or BAMD_BF16");
+    BAMD_WIDE_DTYPE(out_dtype, "out_dtype");
+    BAMD_REQUIRE(n_rows >= 0 && ((z && out) || n_rows == 0), "bad arguments");
+    if (n_rows == 0) return BAMD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype_wide(z_dtype) || latent_in_kernel(h)) return decode_rows(h, z, z_dtype, n_rows, features, int_mask, out, out_dtype, s);
+    const int zd = h->dims[h->L / 2];
+    const size_t orow = (size_t)h->dims[h->L] * dtype_bytes(out_dtype);
+    const int64_t chunk = lat32_chunk(h);
+    for (int64_t r0 = 0; r0 < n_rows; r0 += chunk) {
+        const int64_t rows = n_rows - r0 < chunk ? n_rows - r0 : chunk;
+        int rc = h->lat32.ensure((size_t)rows * zd * sizeof(float));
+        if (rc) return rc;
+        rc = launch_convert((const char *)z + (size_t)r0 * zd * 2, z_dtype, h->lat32.p, BAMD_F32, rows * zd, s);
+        if (rc) return rc;
+        rc = decode_rows(h, h->lat32.p, BAMD_F32, rows, features, int_mask, (char *)out + (size_t)r0 * orow, out_dtype, s);
+        if (rc) return rc;
+    }
+    return BAMD_OK;
+}
+
 int bamd_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features,
                       void *recon, int recon_dtype, double *loss_sum, void *stream) {
     BAMD_CHECK_MODEL(h);
+    BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
+    if (recon) BAMD_WIDE_DTYPE(recon_dtype, "recon_dtype");
     BAMD_REQUIRE(x && loss_sum && n_rows > 0, "bad arguments");
     hipStream_t s = (hipStream_t)stream;
     if (h->pj_state) return pj_forward_loss(h, x, x_dtype, n_rows, features, recon, recon_dtype, loss_sum, s);
@@ -371,6 +443,7 @@ int bamd_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows
 int bamd_fwd_bwd(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features,
                  void *grads, void *stream) {
     BAMD_CHECK_MODEL(h);
+    BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
     BAMD_REQUIRE(grads && n_rows >= 0 && (x || n_rows == 0), "bad arguments");
     hipStream_t s = (hipStream_t)stream;
     if (n_rows == 0) {  // an empty shard of a global batch contributes a zero gradient and zero loss
@@ -394,6 +467,7 @@ int bamd_fwd_bwd(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, con
 int bamd_fwd_bwd_latent(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features,
                         const void *latent_grad, void *grads, void *stream) {
     BAMD_CHECK_MODEL(h);
+    BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
     BAMD_REQUIRE(grads && x && n_rows > 0, "bad arguments");
     if (h->pj_state) {
         set_error("bamd_fwd_bwd_latent: not implemented for PJ_Conv_AE (the sliced-Wasserstein loss is refused for convolutional models)");
@@ -408,7 +482,7 @@ int bamd_fwd_bwd_latent(bamd_handle *h, const void *x, int x_dtype, int64_t n_ro
 
 int bamd_swd(const void *z, const void *prior, const void *proj, int dtype, int64_t n_rows, int z_dim, int n_proj,
              double reg_weight, double *loss_out, void *dz_out, void *stream) {
-    BAMD_REQUIRE(dtype == BAMD_F32 || dtype == BAMD_F64, "bad dtype");
+    BAMD_WIDE_DTYPE(dtype, "dtype");
     return launch_swd(z, prior, proj, dtype, n_rows, z_dim, n_proj, reg_weight, loss_out, dz_out, (hipStream_t)stream);
 }
 
@@ -431,6 +505,7 @@ int bamd_adam_step(bamd_handle *h, void *params, const void *grads, void *m, voi
 int bamd_train_step(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features, void *params,
                     void *grads, void *m, void *v, const bamd_adam *hp, double *loss_accum, void *stream) {
     BAMD_CHECK_MODEL(h);
+    BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
     BAMD_REQUIRE(params && m && v && hp && n_rows >= 0 && (x || n_rows == 0), "bad arguments");
     BAMD_REQUIRE(hp->step >= 1, "step must be >= 1");
     hipStream_t s = (hipStream_t)stream;
@@ -485,7 +560,7 @@ int bamd_train_epoch(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows,
                      void *grads, void *m, void *v, const bamd_adam *hp, double *loss_accum, int64_t *steps_out, void *stream) {
     BAMD_REQUIRE(h && hp, "null argument");
     BAMD_REQUIRE(batch_size > 0 && n_rows >= 0 && (x || n_rows == 0), "bad arguments");
-    BAMD_REQUIRE(x_dtype == BAMD_F32 || x_dtype == BAMD_F64, "bad dtype");
+    BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
     const size_t row_bytes = (size_t)h->dims[0] * (x_dtype == BAMD_F64 ? 8 : 4);
     bamd_adam step_hp = *hp;
     int64_t steps = 0;
@@ -504,7 +579,7 @@ int bamd_train_epoch_dp(bamd_handle *h, const void *x, int x_dtype, const int64_
                         void *params, void *grads, void *m, void *v, const bamd_adam *hp, double *loss_accum, void *stream) {
     BAMD_REQUIRE(h && hp, "null argument");
     BAMD_REQUIRE(n_batches >= 0 && (batch_rows || n_batches == 0), "bad arguments");
-    BAMD_REQUIRE(x_dtype == BAMD_F32 || x_dtype == BAMD_F64, "bad dtype");
+    BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
     const size_t row_bytes = (size_t)h->dims[0] * (x_dtype == BAMD_F64 ? 8 : 4);
     bamd_adam step_hp = *hp;
     int64_t r0 = 0;
@@ -522,18 +597,19 @@ int bamd_train_epoch_dp(bamd_handle *h, const void *x, int x_dtype, const int64_
 
 int bamd_emd_rows(const void *x, const void *recon, int dtype, int64_t n_rows, int n_cols, double *out,
                   void *stream) {
+    BAMD_WIDE_DTYPE(dtype, "dtype");
     return launch_emd_rows(x, recon, dtype, n_rows, n_cols, out, (hipStream_t)stream);
 }
 
 int bamd_error_deltas(const void *x, const void *recon, int dtype, int64_t n_elems, double bound, uint8_t *flags,
                       uint16_t *deltas, void *stream) {
-    BAMD_REQUIRE(dtype == BAMD_F32 || dtype == BAMD_F64, "bad dtype");
+    BAMD_WIDE_DTYPE(dtype, "dtype");
     return launch_error_deltas(x, recon, dtype, n_elems, bound, flags, deltas, (hipStream_t)stream);
 }
 
 int bamd_apply_deltas(void *out, int dtype, int n_cols, const int64_t *rows, const int32_t *cols, const uint16_t *deltas,
                       int64_t count, void *stream) {
-    BAMD_REQUIRE(dtype == BAMD_F32 || dtype == BAMD_F64, "bad dtype");
+    BAMD_WIDE_DTYPE(dtype, "dtype");
     return launch_apply_deltas(out, dtype, n_cols, rows, cols, deltas, count, (hipStream_t)stream);
 }
 
@@ -544,6 +620,7 @@ int bamd_activation_means(bamd_handle *h, const void *x, int x_dtype, int64_t n_
         set_error("bamd_activation_means: PJ_Conv_AE has no activation hooks (the reference model has none either, training.py:287)");
         return BAMD_ERR_UNSUPPORTED;
     }
+    BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
     BAMD_REQUIRE(x && out && n_rows > 0, "bad arguments");
     return generic_activation_means(h, x, x_dtype, n_rows, features, out, max_nodes, (hipStream_t)stream);
 }

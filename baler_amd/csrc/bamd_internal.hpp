@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/baler_amd.h"
+#include "latent_io.hpp"
 
 namespace bamd {
 
@@ -72,6 +73,7 @@ struct bamd_handle {
     bamd::DevBuf slabs;             // per-workgroup partial gradients
     bamd::DevBuf lossp;             // partial loss sums (double)
     bamd::DevBuf gscratch;          // gradient buffer of bamd_train_step() when the caller passes none
+    bamd::DevBuf lat32;             // float32 latent rows either side of the row conversion (16-bit codes on the families that do not fuse it)
     bool params_loaded = false;
     bool fused_ok = false;          // shape is served by the fused register-chained kernels
     void *fused_state = nullptr;    // index maps of the fused path (fused.hip)

@@ -264,14 +264,23 @@ __device__ __forceinline__ void blayer_then_last(const bf8 (&in)[KB][kMB], v4 (&
 // In two halves, so that the NEXT pass's rows can be requested while this pass computes: `issue` only loads (raw
 // values stay in registers: 8 or 16 per batch tile), `finish` normalises, rounds and packs.  IN64 is a template parameter (a
 // run-time dtype branch in front of the loads makes hipcc join the paths with conservative waits).
-template <int D, bool IN64> struct RawBlock { typename std::conditional<IN64, double, float>::type v[8]; };
-template <int D, bool IN64>
-__device__ __forceinline__ void load_block_issue(RawBlock<D, IN64> &raw, const void *x, int64_t row, bool valid, int g) {
-    using T = typename std::conditional<IN64, double, float>::type;
+// IN is the bamd_dtype of the rows: float, double, or -- for the latent codes a decode reads -- binary16 / bfloat16 bit patterns,
+// kept raw until `finish` widens them exactly (latent_io.hpp).
+template <int IN> struct RawElem { using type = typename std::conditional<IN == BAMD_F64, double, typename std::conditional<IN == BAMD_F32, float, uint16_t>::type>::type; };
+template <int D, int IN> struct RawBlock { typename RawElem<IN>::type v[8]; };
+template <int D, int IN>
+__device__ __forceinline__ void load_block_issue(RawBlock<D, IN> &raw, const void *x, int64_t row, bool valid, int g) {
+    using T = typename RawElem<IN>::type;
+    constexpr bool IN64 = IN == BAMD_F64;
     const int64_t base = (valid ? row : 0) * D;
     if (D % 8 == 0) {
         const int f0 = 8 * g < D ? 8 * g : 0;
-        if (IN64) {
+        if (IN >= BAMD_F16) {      // eight codes: one 16-byte load
+            const uint4 t = *(const uint4 *)((const uint16_t *)x + base + f0);
+            const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { raw.v[2 * e] = (T)(w[e] & 0xffffu); raw.v[2 * e + 1] = (T)(w[e] >> 16); }
+        } else if (IN64) {
             const double2 *p = (const double2 *)((const double *)x + base + f0);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const double2 t = p[e]; raw.v[2 * e] = (T)t.x; raw.v[2 * e + 1] = (T)t.y; }
@@ -289,13 +298,14 @@ __device__ __forceinline__ void load_block_issue(RawBlock<D, IN64> &raw, const v
         }
     }
 }
-template <int D, bool IN64>
-__device__ __forceinline__ bf8 load_block_finish(const RawBlock<D, IN64> &raw, int g, const double *feats_lds) {
+template <int D, int IN>
+__device__ __forceinline__ bf8 load_block_finish(const RawBlock<D, IN> &raw, int g, const double *feats_lds) {
     float v[8];
     const int f0 = 8 * g < D ? 8 * g : 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        double d = (double)raw.v[e];
+        double d;
+        if constexpr (IN >= BAMD_F16) d = (double)half_widen<IN == BAMD_BF16>(raw.v[e]); else d = (double)raw.v[e];
         const int f = D % 8 == 0 ? f0 + e : (8 * g + e < D ? 8 * g + e : 0);
         if (feats_lds) d = (d - feats_lds[f]) / feats_lds[32 + f];
         v[e] = (D % 8 == 0 || 8 * g + e < D) ? (float)d : 0.f;
@@ -308,7 +318,7 @@ __device__ __forceinline__ bf8 load_block_finish(const RawBlock<D, IN64> &raw, i
 
 // DEC = false: z = encode(x).  DEC = true: out = decode(z) (+ un-normalise / int truncation), and with xref the
 // squared-error partial of out against (normalised) xref rows (forward_loss).
-template <int F, int Z, bool DEC, bool IN64>
+template <int F, int Z, bool DEC, int IN>
 __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__restrict__ wfrags, const v4 *__restrict__ bias_g,
                                                                  const void *__restrict__ xin, int64_t n,
                                                                  const double *__restrict__ feats, void *__restrict__ out, int out_f64,
@@ -340,13 +350,15 @@ __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__
     // once: SQ_WAIT_ANY 45-51 %); requested BEFORE this pass's stores, so the in-order vmcnt makes the next pass wait for its
     // loads only, not for the stores to drain.
     constexpr int DIN = DEC ? Z : F;
-    RawBlock<DIN, IN64> raw[kMB];
+    constexpr bool IN64 = IN == BAMD_F64;
+    static_assert(DEC || IN <= BAMD_F64, "16-bit rows are latent codes: decode only");
+    RawBlock<DIN, IN> raw[kMB];
     const int64_t pass0 = (int64_t)blockIdx.x * kWaves + wave, pstride = (int64_t)gridDim.x * kWaves;
     auto prefetch = [&](int64_t pass) {
 #pragma unroll
         for (int mb = 0; mb < kMB; ++mb) {
             const int64_t r = pass * kRowsPerPass + 16 * mb + j;
-            load_block_issue<DIN, IN64>(raw[mb], xin, r, pass < npass && r < n, g);
+            load_block_issue<DIN, IN>(raw[mb], xin, r, pass < npass && r < n, g);
         }
     };
     if (pass0 < npass) prefetch(pass0);
@@ -360,7 +372,7 @@ __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__
         if (!DEC) {
             bf8 a0[1][kMB], a2[N::kb(2)][kMB];
 #pragma unroll
-            for (int mb = 0; mb < kMB; ++mb) a0[0][mb] = load_block_finish<DIN, IN64>(raw[mb], g, feats ? fl : nullptr);
+            for (int mb = 0; mb < kMB; ++mb) a0[0][mb] = load_block_finish<DIN, IN>(raw[mb], g, feats ? fl : nullptr);
             if (!IN64) prefetch(pass + pstride);          // float64 rows (16 registers per batch tile): after the widest layer pair
             blayer_pair<N::kb(0), N::nt(0), N::nt(1)>(a0, a2, w + N::f_off(0) * 64, bias + N::b_off(0), w + N::f_off(1) * 64,
                                                       bias + N::b_off(1), g);
@@ -376,7 +388,11 @@ __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__
 #pragma unroll
                 for (int t = 0; t < N::nt(3); ++t) {
                     const int64_t i0 = row[mb] * Z + 16 * t + 4 * g;
-                    if (out_f64) {
+                    if (out_f64 >= BAMD_F16) {      // (out_f64 is the latent's bamd_dtype here) 16-bit codes, rounded to nearest even
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (16 * t + 12 + r < Z || 16 * t + 4 * g + r < Z) ((uint16_t *)out)[i0 + r] = half_bits(out_f64, z[t][mb][r]);
+                    } else if (out_f64) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             if (16 * t + 12 + r < Z || 16 * t + 4 * g + r < Z) ((double *)out)[i0 + r] = (double)z[t][mb][r];
@@ -390,7 +406,7 @@ __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__
         } else {
             bf8 a4[1][kMB], a5[N::kb(5)][kMB], a6[N::kb(6)][kMB];
 #pragma unroll
-            for (int mb = 0; mb < kMB; ++mb) a4[0][mb] = load_block_finish<DIN, IN64>(raw[mb], g, nullptr);
+            for (int mb = 0; mb < kMB; ++mb) a4[0][mb] = load_block_finish<DIN, IN>(raw[mb], g, nullptr);
             if (!IN64) prefetch(pass + pstride);
             blayer<N::kb(4), N::nt(4), true>(a4, a5, w + N::f_off(4) * 64, bias + N::b_off(4), g);
             blayer<N::kb(5), N::nt(5), true>(a5, a6, w + N::f_off(5) * 64, bias + N::b_off(5), g);
@@ -526,13 +542,17 @@ template <int F, int Z> struct BImpl {
             BAMD_HIP(hipMemcpy(st->wsrc[hf].p, wsrc.data(), wsrc.size() * sizeof(int), hipMemcpyHostToDevice));
             BAMD_HIP(hipMemcpy(st->bsrc[hf].p, bsrc.data(), bsrc.size() * sizeof(int), hipMemcpyHostToDevice));
         }
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, false, BAMD_F32>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(0)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, false, BAMD_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(0)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, BAMD_F32>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(1)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, BAMD_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)N::lds_bytes(1)));
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, BAMD_F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)N::lds_bytes(1)));
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, BAMD_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(1)));
         return BAMD_OK;
     }
@@ -542,16 +562,21 @@ template <int F, int Z> struct BImpl {
         const int64_t npass = (n + kRowsPerPass - 1) / kRowsPerPass;
         int64_t wg = (npass + kWaves - 1) / kWaves;
         const int grid = (int)(wg < 1 ? 1 : (wg > st->grid ? st->grid : wg));
-        auto go = [&](auto decv, auto inv) {
-            constexpr bool D_ = decltype(decv)::value, I_ = decltype(inv)::value;
+        auto go = [&](auto decv, auto inv) {      // in_f64 / out_f64 are bamd_dtype codes: 16-bit for the latent side of a decode / an encode
+            constexpr bool D_ = decltype(decv)::value;
+            constexpr int I_ = decltype(inv)::value;
             hipLaunchKernelGGL((bf16_infer_kernel<F, Z, D_, I_>), dim3(grid), dim3(64 * kWaves), N::lds_bytes(D_ ? 1 : 0), s,
                                (const uint4 *)st->w[D_ ? 1 : 0].p, (const v4 *)st->b[D_ ? 1 : 0].p, xin, n, feats, out, out_f64, imask, xref,
                                xref_f64, xref_feats, loss_part);
         };
-        if (dec && in_f64) go(std::true_type(), std::true_type());
-        else if (dec) go(std::true_type(), std::false_type());
-        else if (in_f64) go(std::false_type(), std::true_type());
-        else go(std::false_type(), std::false_type());
+        using i32 = std::integral_constant<int, BAMD_F32>;
+        using i64 = std::integral_constant<int, BAMD_F64>;
+        if (dec && in_f64 == BAMD_F16) go(std::true_type(), std::integral_constant<int, BAMD_F16>());
+        else if (dec && in_f64 == BAMD_BF16) go(std::true_type(), std::integral_constant<int, BAMD_BF16>());
+        else if (dec && in_f64) go(std::true_type(), i64());
+        else if (dec) go(std::true_type(), i32());
+        else if (in_f64) go(std::false_type(), i64());
+        else go(std::false_type(), i32());
         BAMD_HIP(hipGetLastError());
         return grid;
     }
@@ -614,7 +639,7 @@ int bf16_pack(bamd_handle *h, hipStream_t s) {
 
 int bf16_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype, hipStream_t s) {
     Bf16State *st = bstate(h);
-    int rc = st->ops->run(h, st, false, x, x_dtype == BAMD_F64, n, features, z, z_dtype == BAMD_F64, nullptr, nullptr, 0, nullptr,
+    int rc = st->ops->run(h, st, false, x, x_dtype == BAMD_F64, n, features, z, z_dtype, nullptr, nullptr, 0, nullptr,
                           nullptr, s);
     return rc < 0 ? rc : BAMD_OK;
 }
@@ -622,7 +647,7 @@ int bf16_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const dou
 int bf16_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features, const uint8_t *int_mask, void *out,
                 int out_dtype, hipStream_t s) {
     Bf16State *st = bstate(h);
-    int rc = st->ops->run(h, st, true, z, z_dtype == BAMD_F64, n, features, out, out_dtype == BAMD_F64, int_mask, nullptr, 0, nullptr,
+    int rc = st->ops->run(h, st, true, z, z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, nullptr, 0, nullptr,
                           nullptr, s);
     return rc < 0 ? rc : BAMD_OK;
 }

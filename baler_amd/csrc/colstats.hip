@@ -337,7 +337,7 @@ bool aligned16(const void *a, const void *b) { return (((uintptr_t)a | (uintptr_
 
 int check_tables(const char *fn, int dtype, int n_cols, int cut_col) {
     if (dtype != BAMD_F32 && dtype != BAMD_F64) {
-        set_error(std::string(fn) + ": bad dtype");
+        set_error(std::string(fn) + ": dtype must be BAMD_F32 or BAMD_F64 (BAMD_F16 / BAMD_BF16 are latent codes: z_dtype of bamd_encode / bamd_decode only)");
         return BAMD_ERR_INVALID;
     }
     if (n_cols < 1) {

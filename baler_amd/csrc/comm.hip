@@ -156,7 +156,7 @@ int bamd_comm_world(const bamd_handle *h) { return h ? h->comm_world : 0; }
 
 int bamd_allreduce_sum(bamd_handle *h, void *buf, int dtype, int64_t count, void *stream) {
     BAMD_REQUIRE(h && buf && count >= 0, "bad arguments");
-    BAMD_REQUIRE(dtype == BAMD_F32 || dtype == BAMD_F64, "bad dtype");
+    BAMD_REQUIRE(dtype_wide(dtype), "dtype must be BAMD_F32 or BAMD_F64 (BAMD_F16 / BAMD_BF16 are latent codes: z_dtype of bamd_encode / bamd_decode only)");
     DevGuard guard(h->device);
     BAMD_REQUIRE(guard.rc == hipSuccess, "cannot select the handle's device");
     return comm_allreduce_sum(h, buf, dtype, count, (hipStream_t)stream);

@@ -154,6 +154,15 @@ __global__ void convert_k(const TI *__restrict__ x, TO *__restrict__ out, int64_
         out[i] = (TO)x[i];
 }
 
+// 16-bit latent codes on either side (latent_io.hpp): through float32, so a float64 source is rounded to float32 first and then
+// to nearest even in 16 bits, and a 16-bit source is widened exactly.  The layer-wise path's existing staging / output pass, and the
+// one row-conversion launch of the families that write float32 latents into a workspace.
+__global__ void convert_latent_k(const void *__restrict__ x, int sd, void *__restrict__ out, int dd, int64_t count) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
+         i += (int64_t)gridDim.x * blockDim.x)
+        latent_store<float>(out, dd, i, latent_load<float>(x, sd, i));
+}
+
 static inline int ew_grid(int64_t count) {
     int64_t b = (count + 255) / 256;
     return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
@@ -194,7 +203,9 @@ int launch_renormalize(const void *x, int dtype, int64_t n, int c, const double 
 int launch_convert(const void *src, int sd, void *dst, int dd, int64_t count, hipStream_t s) {
     if (count == 0) return BAMD_OK;
     dim3 g(ew_grid(count)), b(256);
-    if (sd == BAMD_F64 && dd == BAMD_F64)
+    if (dtype_half(sd) || dtype_half(dd))
+        hipLaunchKernelGGL(convert_latent_k, g, b, 0, s, src, sd, dst, dd, count);
+    else if (sd == BAMD_F64 && dd == BAMD_F64)
         hipLaunchKernelGGL((convert_k<double, double>), g, b, 0, s, (const double *)src, (double *)dst, count);
     else if (sd == BAMD_F64)
         hipLaunchKernelGGL((convert_k<double, float>), g, b, 0, s, (const double *)src, (float *)dst, count);

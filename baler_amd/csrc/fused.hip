@@ -313,7 +313,9 @@ template <int D> struct RawRows { double v[tiles(D) * 4]; };
 // argument.  Slots map to features exactly as for a D-column table (slot_feature); a slot whose feature is >= dr reads feature 0 and
 // is ZEROED, so that padding meets the zero weights / biases the pack map gives it with a zero on the data side too: the loss, dL/drecon
 // and every weight-gradient product see exact zeros there, and nothing else in a kernel needs to know the real width.
-template <int D, bool RT = false>
+// LAT: the rows are LATENT CODES (the decode prologue): `is_f64` is then a bamd_dtype and may name a 16-bit type, widened exactly
+// (latent_io.hpp).  Table rows (LAT = false) compile to what they always were.
+template <int D, bool RT = false, bool LAT = false>
 __device__ __forceinline__ void load_rows_issue(RawRows<D> &raw, const void *x, int is_f64, int64_t row, bool valid, int lane, int dr = D) {
     // Branch-free: lanes beyond the last row read row 0 and padding slots read feature 0 (always inside the table), so no
     // lane needs an exec-masked branch or a zero fill.  Their values are never used: padding slots meet zero weights and
@@ -336,7 +338,18 @@ __device__ __forceinline__ void load_rows_issue(RawRows<D> &raw, const void *x, 
         if (RT) f = f < dr ? f : 0;
         return f;
     };
-    if (is_f64) {
+    if (LAT && is_f64 >= BAMD_F16) {
+        uint16_t w[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) w[s] = used(s) ? ((const uint16_t *)x)[base + feat(s)] : (uint16_t)0;
+        if (is_f64 == BAMD_BF16) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) raw.v[s] = (double)half_widen<true>(w[s]);
+        } else {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) raw.v[s] = (double)half_widen<false>(w[s]);
+        }
+    } else if (is_f64) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) raw.v[s] = used(s) ? ((const double *)x)[base + feat(s)] : 0.0;
     } else {
@@ -379,11 +392,11 @@ __device__ __forceinline__ void load_rows_finish(v4 (&a)[tiles(D)], RawRows<D> &
     for (int s = 0; s < NS; ++s) a[s >> 2][s & 3] = (float)raw.v[s];
 }
 
-template <int D, bool RT = false>
+template <int D, bool RT = false, bool LAT = false>
 __device__ __forceinline__ void load_rows(v4 (&a)[tiles(D)], const void *x, int is_f64, int64_t row, bool valid,
                                           int lane, const double *__restrict__ feats, int dr = D) {
     RawRows<D> raw;
-    load_rows_issue<D, RT>(raw, x, is_f64, row, valid, lane, dr);
+    load_rows_issue<D, RT, LAT>(raw, x, is_f64, row, valid, lane, dr);
     load_rows_finish<D, RT>(a, raw, valid, lane, feats, dr);
 }
 
@@ -426,13 +439,35 @@ __device__ __forceinline__ void load_rows_wide(v4 (&a)[tiles(D)], const void *x,
     }
 }
 
-template <int D, bool RT = false>
+// 16-bit latent codes of one row tile: the lane's float32 values rounded to nearest even (latent_io.hpp) and stored where the
+// float32 codes would go, 2 bytes each.  (Every latent the register chain is instantiated for is narrower than a full aligned tile,
+// so -- like the float32 codes of those shapes -- they go out as element stores.)
+template <int D, bool RT, bool BF>
+__device__ __forceinline__ void store_rows_half(const v4 (&a)[tiles(D)], void *out, int64_t row, int lane, int dr) {
+    const int g = lane >> 4;
+    uint16_t *o = (uint16_t *)out + row * (RT ? dr : D);
+#pragma unroll
+    for (int t = 0; t < tiles(D); ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int f = slot_feature(D, t, g, r);
+            if (f >= 0 && (!RT || f < dr)) o[f] = half_bits<BF>(a[t][r]);
+        }
+}
+
+// LAT: the rows are LATENT CODES (the encode epilogue): `is_f64` is then a bamd_dtype and may name a 16-bit type.
+template <int D, bool RT = false, bool LAT = false>
 __device__ __forceinline__ void store_rows(const v4 (&a)[tiles(D)], void *out, int is_f64, int64_t row, bool valid,
                                            int lane, const double *__restrict__ renorm, const uint8_t *__restrict__ imask, int dr = D) {
     // ONE lane mask (valid row) around everything and the uniform dtype / renorm tests outside the element loops; a slot
     // needs its own lane test only if it is padding on SOME lane group (the last register of a partial r-major tile).
     const int g = lane >> 4;
     if (!valid) return;
+    if (LAT && is_f64 >= BAMD_F16) {
+        if (is_f64 == BAMD_BF16) store_rows_half<D, RT, true>(a, out, row, lane, dr);
+        else store_rows_half<D, RT, false>(a, out, row, lane, dr);
+        return;
+    }
     double v[tiles(D)][4];
 #pragma unroll
     for (int t = 0; t < tiles(D); ++t)
@@ -527,7 +562,7 @@ __global__ void __launch_bounds__(256) infer_kernel(const v4 *packed, const void
             fwd_layer<N, S, 2>(a2, a3, ring, ws, bias_lds, lane);
             fwd_layer<N, S, 3>(a3, a4, ring, ws, bias_lds, lane);
             if (KIND == K_ENCODE) {
-                store_rows<Z, RT>(a4, out, out_f64, row, valid, lane, nullptr, nullptr, zr);
+                store_rows<Z, RT, true>(a4, out, out_f64, row, valid, lane, nullptr, nullptr, zr);
             } else {
                 v4 a5[4], a6[7], a7[13], a8[tiles(F)];
                 fwd_layer<N, S, 4>(a4, a5, ring, ws, bias_lds, lane);
@@ -548,7 +583,7 @@ __global__ void __launch_bounds__(256) infer_kernel(const v4 *packed, const void
             }
         } else {
             v4 a4[tiles(Z)], a5[4], a6[7], a7[13], a8[tiles(F)];
-            load_rows<Z, RT>(a4, xin, in_f64, row, valid, lane, nullptr, zr);
+            load_rows<Z, RT, true>(a4, xin, in_f64, row, valid, lane, nullptr, zr);
             fwd_layer<N, S, 4>(a4, a5, ring, ws, bias_lds, lane);
             fwd_layer<N, S, 5>(a5, a6, ring, ws, bias_lds, lane);
             fwd_layer<N, S, 6>(a6, a7, ring, ws, bias_lds, lane);
@@ -586,8 +621,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     {
         const int64_t p0 = (int64_t)blockIdx.x * 4 + wave;
         const int64_t q0 = p0 * 32 + (lane & 15), q1 = q0 + 16;
-        load_rows_issue<DIN, RT>(ra, xin, in_f64, q0, q0 < n, lane, (KIND == K_ENCODE ? fr : zr));
-        load_rows_issue<DIN, RT>(rb, xin, in_f64, q1, q1 < n, lane, (KIND == K_ENCODE ? fr : zr));
+        load_rows_issue<DIN, RT, KIND == K_DECODE>(ra, xin, in_f64, q0, q0 < n, lane, (KIND == K_ENCODE ? fr : zr));
+        load_rows_issue<DIN, RT, KIND == K_DECODE>(rb, xin, in_f64, q1, q1 < n, lane, (KIND == K_ENCODE ? fr : zr));
     }
     for (int64_t pr = (int64_t)blockIdx.x * 4 + wave; pr < npair; pr += (int64_t)gridDim.x * 4) {
         const int64_t r0 = pr * 32 + (lane & 15), r1 = r0 + 16;
@@ -607,16 +642,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             __builtin_amdgcn_sched_barrier(0);
             fwd_layer2<N, S, 2>(a2, b2, a3, b3, ring, ws, bias_lds, lane);
             fwd_layer2<N, S, 3>(a3, b3, a4, b4, ring, ws, bias_lds, lane);
-            store_rows<Z, RT>(a4, out, out_f64, r0, v0, lane, nullptr, nullptr, zr);
-            store_rows<Z, RT>(b4, out, out_f64, r1, v1, lane, nullptr, nullptr, zr);
+            store_rows<Z, RT, true>(a4, out, out_f64, r0, v0, lane, nullptr, nullptr, zr);
+            store_rows<Z, RT, true>(b4, out, out_f64, r1, v1, lane, nullptr, nullptr, zr);
         } else {
             v4 a4[tiles(Z)], b4[tiles(Z)], a5[4], b5[4], a6[7], b6[7], a7[13], b7[13], a8[tiles(F)], b8[tiles(F)];
             load_rows_finish<Z, RT>(a4, ra, v0, lane, nullptr, zr);
             load_rows_finish<Z, RT>(b4, rb, v1, lane, nullptr, zr);
             fwd_layer2<N, S, 4>(a4, b4, a5, b5, ring, ws, bias_lds, lane);
             __builtin_amdgcn_sched_barrier(0);
-            load_rows_issue<Z, RT>(ra, xin, in_f64, n0, n0 < n, lane, zr);
-            load_rows_issue<Z, RT>(rb, xin, in_f64, n1, n1 < n, lane, zr);
+            load_rows_issue<Z, RT, true>(ra, xin, in_f64, n0, n0 < n, lane, zr);
+            load_rows_issue<Z, RT, true>(rb, xin, in_f64, n1, n1 < n, lane, zr);
             __builtin_amdgcn_sched_barrier(0);
             fwd_layer2<N, S, 5>(a5, b5, a6, b6, ring, ws, bias_lds, lane);
             fwd_layer2<N, S, 6>(a6, b6, a7, b7, ring, ws, bias_lds, lane);
@@ -3813,13 +3848,13 @@ template <int F, int Z, bool RT = false> struct Impl {
         constexpr int extra_lds = 0;
         if (F <= 64 && infer_pair()) {
             hipLaunchKernelGGL((infer2_kernel<F <= 64 ? F : 24, Z, K_ENCODE, RT>), dim3(infer_grid((n + 1) / 2)), dim3(256), 0, s,
-                               (const v4 *)h->packed.p, x, x_dtype == BAMD_F64, n, features, z, z_dtype == BAMD_F64,
+                               (const v4 *)h->packed.p, x, x_dtype == BAMD_F64, n, features, z, z_dtype,
                                (const uint8_t *)nullptr, fr(h), zr(h));
             BAMD_HIP(hipGetLastError());
             return BAMD_OK;
         }
         hipLaunchKernelGGL((infer_kernel<F, Z, K_ENCODE, RT>), dim3(infer_grid(n)), dim3(256), extra_lds, s, (const v4 *)h->packed.p, x,
-                           x_dtype == BAMD_F64, n, features, z, z_dtype == BAMD_F64, (const uint8_t *)nullptr, (double *)nullptr, fr(h), zr(h));
+                           x_dtype == BAMD_F64, n, features, z, z_dtype, (const uint8_t *)nullptr, (double *)nullptr, fr(h), zr(h));
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
@@ -3827,12 +3862,12 @@ template <int F, int Z, bool RT = false> struct Impl {
                       void *out, int out_dtype, hipStream_t s) {
         if (F <= 64 && infer_pair()) {
             hipLaunchKernelGGL((infer2_kernel<F <= 64 ? F : 24, Z, K_DECODE, RT>), dim3(infer_grid((n + 1) / 2)), dim3(256), 0, s,
-                               (const v4 *)h->packed.p, z, z_dtype == BAMD_F64, n, features, out, out_dtype == BAMD_F64, int_mask, fr(h), zr(h));
+                               (const v4 *)h->packed.p, z, z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, fr(h), zr(h));
             BAMD_HIP(hipGetLastError());
             return BAMD_OK;
         }
         hipLaunchKernelGGL((infer_kernel<F, Z, K_DECODE, RT>), dim3(infer_grid(n)), dim3(256), 0, s, (const v4 *)h->packed.p, z,
-                           z_dtype == BAMD_F64, n, features, out, out_dtype == BAMD_F64, int_mask, (double *)nullptr, fr(h), zr(h));
+                           z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, (double *)nullptr, fr(h), zr(h));
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
@@ -4732,6 +4767,12 @@ void fused_wide_set_dz16(bamd_handle *h, bool on) {
 int fused_wide_train_backward(bamd_handle *h, int64_t rows, float *const *y, float *const *dz, const float *dz_latent, hipStream_t s) {
     if (!fused_wide_train(h)) return BAMD_ERR_UNSUPPORTED;
     return state_of(h)->ops->wide_bwd(h, rows, y, dz, dz_latent, s);
+}
+
+// 16-bit latent codes: the register-chain kernels (infer_kernel / infer2_kernel, exact shapes and run-time-width classes) round and
+// widen them in their own row store / load; the wide-layer kernels keep float32 / float64 latents (api.hip converts around them).
+bool fused_latent_in_kernel(const bamd_handle *h) {
+    return h->fused_ok && h->fused_state && ((const FusedState *)h->fused_state)->ops->wide_fwd == nullptr;
 }
 
 int fused_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype,

@@ -13,6 +13,7 @@ bool fused_has_bf16_kernels(const bamd_handle *h);        // the shape is one of
 void fused_params_changed(bamd_handle *h);       // an optimiser step changed h->params / h->packed: lazily refreshed copies are stale
 // scatter lists (CSR over parameters) into h->packed for the fused Adam+pack kernel; all null when !fused_ok
 void fused_scatter(bamd_handle *h, const int **sc_off, const int **sc_idx, void **packed);
+bool fused_latent_in_kernel(const bamd_handle *h);      // this handle's fused encode / decode kernels store / load 16-bit latent codes themselves
 int fused_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z,
                  int z_dtype, hipStream_t s);
 int fused_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features,

@@ -1118,7 +1118,7 @@ static int carve(bamd_handle *h, int64_t n, bool need_grad, Work<T> &wk) {
 template <typename T>
 static int stage_input(bamd_handle *h, const void *x, int x_dtype, int64_t row0, int64_t rows, int width,
                        const double *features, T *dst, hipStream_t s) {
-    size_t es = x_dtype == BAMD_F64 ? 8 : 4;
+    size_t es = dtype_bytes(x_dtype);      // (16-bit latent codes of a decode: widened by the staging pass itself)
     const char *src = (const char *)x + (size_t)row0 * width * es;
     int td = sizeof(T) == 8 ? BAMD_F64 : BAMD_F32;
     if (features) return launch_normalize(src, x_dtype, rows, width, features, dst, td, s);
@@ -1148,7 +1148,7 @@ static int forward_T(bamd_handle *h, const void *x, int x_dtype, int64_t n, cons
     if (rc) return rc;
     int td = sizeof(T) == 8 ? BAMD_F64 : BAMD_F32;
     int win = h->dims[l0], wout = h->dims[l1];
-    size_t oes = out_dtype == BAMD_F64 ? 8 : 4;
+    size_t oes = dtype_bytes(out_dtype);   // (16-bit latent codes of an encode: rounded by the output pass itself)
     for (int64_t r0 = 0; r0 < n; r0 += wk.chunk) {
         int64_t rows = n - r0 < wk.chunk ? n - r0 : wk.chunk;
         rc = stage_input<T>(h, x, x_dtype, r0, rows, win, features, wk.y[l0], s);

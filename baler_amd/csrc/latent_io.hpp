@@ -1,0 +1,54 @@
+// Latent codes in caller memory: the ONE definition of how a latent element is stored and loaded for every bamd_dtype
+// (float, double, IEEE binary16, bfloat16).  Every inference family's encode epilogue and decode prologue goes through
+// latent_store / latent_load (or their 16-bit halves where the float32 / float64 path of a kernel stays as it was).
+//
+// Rounding rule (include/baler_amd.h, bamd_dtype): a 16-bit code is the round-to-nearest-even conversion of the value the
+// handle would have stored as FLOAT32 -- a float64 latent is rounded to float32 first, then to 16 bits, which is what
+// t.to(float32).to(float16 / bfloat16) does.  NaN stays NaN, +-inf stays +-inf, float16 overflow gives +-inf (no saturation)
+// and float16 subnormals are produced.  Widening a 16-bit code is exact.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/baler_amd.h"
+
+namespace bamd {
+
+inline bool dtype_wide(int d) { return d == BAMD_F32 || d == BAMD_F64; }        // legal for every dtype argument
+inline bool dtype_half(int d) { return d == BAMD_F16 || d == BAMD_BF16; }       // legal as the latent of bamd_encode / bamd_decode only
+inline size_t dtype_bytes(int d) { return d == BAMD_F64 ? 8 : d == BAMD_F32 ? 4 : 2; }
+
+#if defined(__HIPCC__)
+// float32 -> binary16 bits: v_cvt_f16_f32, round to nearest even (the truncating pack conversion is NOT used anywhere)
+__device__ __forceinline__ uint16_t f16_bits(float v) { return __builtin_bit_cast(uint16_t, (_Float16)v); }
+__device__ __forceinline__ float f16_widen(uint16_t u) { return (float)__builtin_bit_cast(_Float16, u); }
+// float32 -> bfloat16 bits: round to nearest even on the integer pattern; NaN -> the canonical quiet NaN 0x7fc0 (torch's)
+__device__ __forceinline__ uint16_t bf16_bits(float v) {
+    uint32_t u = __builtin_bit_cast(uint32_t, v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)0x7fc0;
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+__device__ __forceinline__ float bf16_widen(uint16_t u) { return __builtin_bit_cast(float, (uint32_t)u << 16); }
+
+// BF: the code is bfloat16 (else binary16)
+template <bool BF> __device__ __forceinline__ uint16_t half_bits(float v) { return BF ? bf16_bits(v) : f16_bits(v); }
+template <bool BF> __device__ __forceinline__ float half_widen(uint16_t u) { return BF ? bf16_widen(u) : f16_widen(u); }
+__device__ __forceinline__ uint16_t half_bits(int dtype, float v) { return dtype == BAMD_BF16 ? bf16_bits(v) : f16_bits(v); }
+__device__ __forceinline__ float half_widen(int dtype, uint16_t u) { return dtype == BAMD_BF16 ? bf16_widen(u) : f16_widen(u); }
+// element i of a latent buffer of `dtype`; S is the kernel's compute scalar (float or double)
+template <typename S> __device__ __forceinline__ void latent_store(void *base, int dtype, int64_t i, S v) {
+    if (dtype == BAMD_F64) ((double *)base)[i] = (double)v;
+    else if (dtype == BAMD_F32) ((float *)base)[i] = (float)v;
+    else ((uint16_t *)base)[i] = half_bits(dtype, (float)v);
+}
+template <typename S> __device__ __forceinline__ S latent_load(const void *base, int dtype, int64_t i) {
+    if (dtype == BAMD_F64) return (S)((const double *)base)[i];
+    if (dtype == BAMD_F32) return (S)((const float *)base)[i];
+    return (S)half_widen(dtype, ((const uint16_t *)base)[i]);
+}
+#endif
+
+}  // namespace bamd

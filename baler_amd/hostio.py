@@ -36,6 +36,64 @@ NP_OF_TORCH = {torch.float32: np.float32, torch.float64: np.float64, torch.float
                torch.uint8: np.uint8, torch.int32: np.int32, torch.int64: np.int64}
 
 
+# ---- 16-bit latent codes in compressed.npz --------------------------------------------------------------------------------
+# config.latent_dtype -> the torch dtype of the latent buffer.  float16 codes are stored as a numpy float16 `data`; numpy has no
+# bfloat16, so those are stored as their uint16 bit patterns plus the key latent_dtype = "bfloat16".  Archives without the key are
+# recognised by data.dtype (float16 / float32 / float64), so everything written before the key existed loads as it always did.
+LATENT_DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16}
+
+
+def parse_latent_dtype(value):
+    """config.latent_dtype -> None (codes at the working precision, the default) | "float16" | "bfloat16"; else ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, str) and value in LATENT_DTYPES:
+        return value
+    raise ValueError(f"latent_dtype must be None, \"float16\" or \"bfloat16\", got {value!r}")
+
+
+def bf16_bits(a):
+    """float32 values -> bfloat16 bit patterns (uint16), round to nearest even, NaN -> 0x7fc0: what torch.bfloat16 stores."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    r = ((u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+    r[(u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)] = 0x7FC0
+    return r
+
+
+def bf16_widen(bits):
+    """bfloat16 bit patterns (uint16) -> the float32 values they stand for (exact)."""
+    return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def latent_to_archive(codes, latent_dtype=None):
+    """The latent member(s) of compressed.npz as np.savez keywords.  codes: float32 / float64 (latent_dtype None), numpy float16
+    ("float16"), or the uint16 bit patterns of bfloat16 codes ("bfloat16")."""
+    latent_dtype = parse_latent_dtype(latent_dtype)
+    if latent_dtype is None:
+        return {"data": codes}
+    if latent_dtype == "float16":
+        if codes.dtype != np.float16:
+            raise ValueError(f"float16 latent codes expected, got {codes.dtype}")
+        return {"data": codes}
+    if codes.dtype != np.uint16:
+        raise ValueError(f"bfloat16 latent codes travel as uint16 bit patterns, got {codes.dtype}")
+    return {"data": codes, "latent_dtype": np.array("bfloat16")}
+
+
+def latent_from_archive(data, archive_keys, read_key):
+    """-> (host array to upload, torch dtype of 16-bit codes or None).  ``data``: the archive's `data` member (memory-mapped or
+    loaded), ``archive_keys``: the archive's member names, ``read_key(name)``: loads one.  bfloat16 bit patterns come back viewed
+    as float16 -- a 2-byte carrier that every copy moves verbatim; the device tensor is re-viewed as bfloat16."""
+    if "latent_dtype" in archive_keys:
+        name = str(read_key("latent_dtype"))
+        if name != "bfloat16" or data.dtype != np.uint16:
+            raise ValueError(f"compressed archive: latent_dtype = {name!r} with data of {data.dtype} is not a format this version writes")
+        return data.view(np.float16), torch.bfloat16
+    if data.dtype == np.float16:
+        return data, torch.float16
+    return data, None
+
+
 def _pool():
     global _POOL
     if _POOL is None:
@@ -226,22 +284,25 @@ def _staging(slot, rows, tail, dtype):
     return buf[:need].view(dtype).view((rows,) + tuple(tail))
 
 
-def _device_dtype(np_dtype):
+def _device_dtype(np_dtype, keep_half=False):
     """float32 / float64 tables keep their dtype; anything else is converted to float64 on the host chunk
-    (the reference does the same implicitly when it builds float64 tensors, training.py:230)."""
+    (the reference does the same implicitly when it builds float64 tensors, training.py:230).  keep_half: float16 stays float16
+    (16-bit latent codes; tables never take this route)."""
+    if keep_half and np_dtype == np.float16:
+        return torch.float16, np.float16
     if np_dtype == np.float32:
         return torch.float32, np.float32
     return torch.float64, np.float64
 
 
-def upload_rows(src, plan=None, device=None, chunk_bytes=None):
+def upload_rows(src, plan=None, device=None, chunk_bytes=None, keep_half=False):
     """Rows of host array ``src`` selected by ``plan`` (default: all) -> ONE contiguous device tensor of shape
     (plan.count,) + src.shape[1:], float32 or float64.  Double-buffered: pinned staging x 2 + a copy stream."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
     plan = plan or RowPlan.whole(src.shape[0])
-    t_dtype, h_dtype = _device_dtype(src.dtype)
+    t_dtype, h_dtype = _device_dtype(src.dtype, keep_half)
     tail = tuple(src.shape[1:])
     row_elems = int(np.prod(tail)) if tail else 1
     out = torch.empty((plan.count,) + tail, dtype=t_dtype, device=device)

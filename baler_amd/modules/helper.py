@@ -331,6 +331,35 @@ def _derive_sizes(config, data_shape, names_len):
                     + str(config.data_dimension))
 
 
+def latent_dtype_of(config):
+    """config.latent_dtype -> None | "float16" | "bfloat16" (hostio.parse_latent_dtype; anything else: ValueError)."""
+    return hostio.parse_latent_dtype(getattr(config, "latent_dtype", None))
+
+
+def _check_float16_range(h, flat, feats, out, world):
+    """config.latent_dtype = "float16": a latent beyond +-65504 is stored as +-inf and decodes to garbage.  Before anything leaves the
+    device: count the inf codes (one accumulation on the device, one read); only if there are any, encode the affected row blocks once
+    more at float32 and count those whose float32 latent is finite; refuse to go on if there are any.  Every rank takes part (the
+    counts are summed over the ranks) and every rank raises."""
+    n_inf = torch.isinf(out).sum().to(torch.float64).reshape(1)
+    if world > 1:
+        bdist.allreduce_sum(n_inf)
+    if int(n_inf.item()) == 0:
+        return
+    bad = torch.zeros(1, dtype=torch.float64, device=out.device)
+    for s in range(0, out.shape[0], ROW_BLOCK):
+        e = min(s + ROW_BLOCK, out.shape[0])
+        z32 = h.encode(flat[s:e], features=feats, out_dtype=torch.float32)
+        bad += (torch.isinf(out[s:e]) & torch.isfinite(z32)).sum()
+    if world > 1:
+        bdist.allreduce_sum(bad)
+    count = int(bad.item())
+    if count:
+        raise ValueError(f"latent_dtype = \"float16\": {count} latent codes of this model are finite but beyond the float16 range "
+                         "(|z| > 65504) and would be stored as +-inf; no archive is written.  Use latent_dtype = \"bfloat16\" "
+                         "(float32's range at 8 bits of precision) or leave latent_dtype unset.")
+
+
 def compress(model_path, config):
     """reference helper.py:473-616.  Returns (compressed ndarray, batches, deltas, indices); the last three are
     empty lists unless ``config.save_error_bounded_deltas`` (then: batch numbers, one float16 array per batch and
@@ -342,8 +371,14 @@ def compress(model_path, config):
     Pipeline per rank: file -> pinned staging -> HBM (double buffered), column min/max, then per ROW_BLOCK one
     ``bamd_encode`` with the normalisation fused into the load (evaluated in float64 on the UNCAST source values, as
     the reference normalises before it casts, helper.py:500-504,560-563), the download of block k overlapping the
-    encode of block k+1."""
+    encode of block k+1.
+
+    ``config.latent_dtype`` = "float16" / "bfloat16": the latent buffer has that dtype -- bamd_encode rounds the codes on the device, so
+    the gather, the download and the archive move 2 bytes per code; float16 codes come back as a numpy float16 array, bfloat16 codes
+    as their uint16 bit patterns (hostio.latent_to_archive).  The deltas side channel is computed from decode() of the ROUNDED codes,
+    which is what decompress will decode."""
     want_deltas = bool(getattr(config, "save_error_bounded_deltas", False))
+    latent_dtype = latent_dtype_of(config)          # (a bad value fails here, before any GPU work)
     rank, world = bdist.rank_world()
     src, original_shape = _open_table(config.input_path, getattr(config, "convert_to_blocks", None) or None)
     names = np.load(config.input_path)["names"]
@@ -370,7 +405,7 @@ def compress(model_path, config):
     model.eval()
     h = model.handle()
     n_local = flat.shape[0]
-    out = torch.empty((n_local, config.latent_space_size), dtype=work_dtype, device=flat.device)
+    out = torch.empty((n_local, config.latent_space_size), dtype=hostio.LATENT_DTYPES.get(latent_dtype, work_dtype), device=flat.device)
     if want_deltas:
         flags = torch.empty((n_local, n_features), dtype=torch.uint8, device=flat.device)
         deltas = torch.empty((n_local, n_features), dtype=torch.float16, device=flat.device)
@@ -383,11 +418,16 @@ def compress(model_path, config):
             # the side channel compares decode(encode(x)) with the NORMALISED input (helper.py:589-606)
             xn = native.normalize(flat[s:e], feats, out_dtype=work_dtype) if feats is not None else flat[s:e]
             h.encode(xn, out=out[s:e])
-            flags[s:e], deltas[s:e] = native.error_deltas(xn, h.decode(out[s:e]), config.error_bounded_requirement)
+            flags[s:e], deltas[s:e] = native.error_deltas(xn, h.decode(out[s:e], out_dtype=xn.dtype), config.error_bounded_requirement)
         ev = torch.cuda.Event()
         ev.record()
         ready.append((e, ev))
-    compressed = _gather_rows(out, n_total, world, ready)
+    if latent_dtype == "float16":       # before the gather and the download: an overflowing run fails without moving the codes
+        _check_float16_range(h, flat, feats, out, world)
+    # bfloat16 codes travel as a float16-typed view: a 2-byte carrier every collective and numpy know; no copy interprets it
+    compressed = _gather_rows(out.view(torch.float16) if latent_dtype == "bfloat16" else out, n_total, world, ready)
+    if latent_dtype == "bfloat16":
+        compressed = compressed.view(np.uint16)
     if not want_deltas:
         return compressed, [], [], []
     flags = _gather_rows(flags, n_total, world)
@@ -483,6 +523,8 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
     data = hostio.open_npz_array(input_path, "data")     # memory-mapped when stored: a rank reads only its rows
     names = loaded["names"]
     normalization_features = loaded["normalization_features"]
+    # 16-bit codes are recognised from the ARCHIVE (data.dtype / its latent_dtype key), never from the config
+    data, code_dtype = hostio.latent_from_archive(data, loaded.files, lambda k: loaded[k])
     latent_space_size = data.shape[1]
     model_dict = torch.load(str(model_path), map_location="cpu")
     number_of_columns = len(model_dict[list(model_dict.keys())[-1]])  # len(de4.bias), helper.py:668-674
@@ -500,7 +542,11 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
     n_total = data.shape[0]
     lo, hi = bdist.shard_rows(n_total, rank, world)
     # this rank's latent rows only, through pinned double-buffered staging
-    z = hostio.upload_rows(data, hostio.RowPlan.contiguous(n_total, rank, world), get_device())
+    z = hostio.upload_rows(data, hostio.RowPlan.contiguous(n_total, rank, world), get_device(), keep_half=code_dtype is not None)
+    if code_dtype is not None:
+        z = z.view(code_dtype)
+    # what the decoder writes without the fused epilogue: the codes' own dtype, or the working precision compress() had for 16-bit codes
+    plain_dtype = z.dtype if code_dtype is None else (torch.float32 if config.data_dimension == 2 else torch.float64)
     want_deltas = bool(getattr(config, "save_error_bounded_deltas", False))
     r_feats = r_mask = None
     if renorm is not None:
@@ -508,7 +554,7 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
         if renorm[1] is not None:
             r_mask = torch.as_tensor(np.asarray(renorm[1], dtype=np.uint8), device=z.device).contiguous()
     fuse = renorm is not None and not want_deltas
-    out = torch.empty((hi - lo, number_of_columns), dtype=torch.float64 if fuse else z.dtype, device=z.device)
+    out = torch.empty((hi - lo, number_of_columns), dtype=torch.float64 if fuse else plain_dtype, device=z.device)
     ready = []
     for s in range(0, hi - lo, ROW_BLOCK):
         e = min(s + ROW_BLOCK, hi - lo)

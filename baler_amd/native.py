@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BALER_AMD_LIB", os.path.join(_HERE, "libbaler_amd.so"))  # override: kernel A/B experiments
 
 F32, F64 = 0, 1
+F16, BF16 = 2, 3        # 16-bit latent codes: the z of bamd_encode / bamd_decode only (include/baler_amd.h, bamd_dtype)
 MODE_F32, MODE_F64, MODE_BF16 = 0, 1, 2
 MODE_NAMES = {"fp32": MODE_F32, "f32": MODE_F32, "fp64": MODE_F64, "f64": MODE_F64, "bf16": MODE_BF16}
 ACT_LEAKY_RELU, ACT_RELU = 0, 1
@@ -118,6 +119,15 @@ def _dt(t):
     if t.dtype == torch.float64:
         return F64
     raise NativeError(f"unsupported tensor dtype {t.dtype}")
+
+
+def _dt_latent(t):
+    """dtype code of a latent tensor: float32 / float64 as everywhere, or the 16-bit code types of bamd_encode / bamd_decode."""
+    if t.dtype == torch.float16:
+        return F16
+    if t.dtype == torch.bfloat16:
+        return BF16
+    return _dt(t)
 
 
 def _dev_tensor(t):
@@ -446,18 +456,24 @@ class Handle:
         return out
 
     def encode(self, x, features=None, out_dtype=None, out=None):
+        """z = encode(x).  out_dtype (or the dtype of ``out``): float32 / float64, or torch.float16 / torch.bfloat16 for 16-bit
+        codes -- the round-to-nearest-even conversion of the float32 codes, made on the device by bamd_encode (inside the encode kernel
+        for the fp32 register chain, bf16.hip and the layer-wise path; one conversion launch behind a float32 workspace otherwise)."""
         x = _dev_tensor(x)
         self._mine(x, features)
         out = self._out(out, x.shape[0], self.z_dim, out_dtype or x.dtype, x.device)
-        _check(lib().bamd_encode(self._h, _ptr(x), _dt(x), x.shape[0], _ptr(features), _ptr(out), _dt(out),
+        _check(lib().bamd_encode(self._h, _ptr(x), _dt(x), x.shape[0], _ptr(features), _ptr(out), _dt_latent(out),
                                  self._s()), "bamd_encode")
         return out
 
     def decode(self, z, features=None, int_mask=None, out_dtype=None, out=None):
+        """out = decode(z).  z may hold float16 / bfloat16 codes: they are widened exactly, the result is that of the widened
+        float32 codes bit for bit (default output dtype then: float32)."""
         z = _dev_tensor(z)
         self._mine(z, features, int_mask)
-        out = self._out(out, z.shape[0], self.dims[-1], out_dtype or z.dtype, z.device)
-        _check(lib().bamd_decode(self._h, _ptr(z), _dt(z), z.shape[0], _ptr(features), _ptr(int_mask),
+        default = z.dtype if z.dtype in (torch.float32, torch.float64) else torch.float32
+        out = self._out(out, z.shape[0], self.dims[-1], out_dtype or default, z.device)
+        _check(lib().bamd_decode(self._h, _ptr(z), _dt_latent(z), z.shape[0], _ptr(features), _ptr(int_mask),
                                  _ptr(out), _dt(out), self._s()), "bamd_decode")
         return out
 

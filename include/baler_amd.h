@@ -49,8 +49,16 @@ typedef enum bamd_status {
     BAMD_ERR_UNSUPPORTED = -5  /* feature not available in this compute mode */
 } bamd_status;
 
-/* element type of a caller buffer */
-typedef enum bamd_dtype { BAMD_F32 = 0, BAMD_F64 = 1 } bamd_dtype;
+/* element type of a caller buffer.  BAMD_F16 (IEEE binary16) and BAMD_BF16 (bfloat16) are STORAGE types of latent codes and are
+ * legal in exactly two places: z_dtype of bamd_encode (the output) and z_dtype of bamd_decode (the input).  Every other dtype
+ * argument of every function (x_dtype, out_dtype, recon_dtype, bamd_load_params, the normalisation / statistics / deltas / swd
+ * entry points, bamd_allreduce_sum, the training calls) returns BAMD_ERR_INVALID for them, with a message that names the
+ * argument, before anything is written to a caller buffer.
+ * Rounding: a 16-bit code is the IEEE round-to-nearest-even conversion of the value the same handle would have stored as FLOAT32
+ * (a BAMD_MODE_F64 handle rounds its float64 latent to float32 first, then to 16 bits: t.to(float32).to(float16 / bfloat16)).  NaN
+ * stays NaN, +-inf stays +-inf, a float16 overflow gives +-inf (no saturation), float16 subnormals are produced, not flushed.
+ * Widening a code on bamd_decode is exact: the result equals bamd_decode of the widened float32 codes bit for bit. */
+typedef enum bamd_dtype { BAMD_F32 = 0, BAMD_F64 = 1, BAMD_F16 = 2, BAMD_BF16 = 3 } bamd_dtype;
 
 /* arithmetic the Linear layers run in.  F32 = v_mfma_f32_16x16x4_f32 (exact fp32, the parity mode:
  * outputs within 1e-5 rel. of the fp64 reference).  F64 = v_mfma_f64_16x16x4_f64 (long-horizon
@@ -194,12 +202,16 @@ int bamd_renormalize(const void *x, int dtype, int64_t n_rows, int n_cols, const
  * Replaces: AE.encode (models.py:141-145) as driven by helper.compress's loop (helper.py:583-611).
  * x: (n_rows, n_features) row-major, x_dtype.  If features != NULL the rows are min-max normalised
  * on load with features = [min ; range] (device, float64) -- the fused form of helper.py:500-504.
- * z: (n_rows, z_dim) row-major, z_dtype. */
+ * z: (n_rows, z_dim) row-major, z_dtype: BAMD_F32 / BAMD_F64, or BAMD_F16 / BAMD_BF16 for 16-bit codes (2 bytes per element,
+ * rounded as described at bamd_dtype; the conversion is part of the encode launch for the fp32 register-chain, bf16 and
+ * layer-wise kernels, and one row-conversion launch behind a float32 workspace for the wide-layer kernels, the fp64 chain,
+ * FPGA_prototype_model and PJ_Conv_AE).  x_dtype is BAMD_F32 or BAMD_F64. */
 int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features,
                 void *z, int z_dtype, void *stream);
 /* Replaces: AE.decode (models.py:147-152) as driven by helper.decompress (helper.py:700-723), with
  * the optional un-normalise + int-column truncation epilogue of baler.py:420-435 fused in when
- * features != NULL (int_mask may still be NULL). */
+ * features != NULL (int_mask may still be NULL).  z_dtype may be BAMD_F16 / BAMD_BF16: the codes are widened exactly on load and
+ * the result is bit-identical to decoding the widened float32 codes.  out_dtype is BAMD_F32 or BAMD_F64. */
 int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, const double *features,
                 const uint8_t *int_mask, void *out, int out_dtype, void *stream);
 /* Replaces: AE.forward (models.py:154-156) + utils.mse_sum_loss_l1(validate=True)
