@@ -27,13 +27,17 @@ void set_error(const std::string &msg);
         }                                                                                   \
     } while (0)
 
-#define BAMD_REQUIRE(cond, msg)                                                             \
+// `fn`: the public entry point the message names (callers match on bamd_last_error()); a helper shared by several passes theirs on
+#define BAMD_REQUIRE_AS(fn, cond, msg)                                                      \
     do {                                                                                    \
         if (!(cond)) {                                                                      \
-            bamd::set_error(std::string(__func__) + ": " + (msg));                          \
+            bamd::set_error(std::string(fn) + ": " + (msg));                                \
             return BAMD_ERR_INVALID;                                                        \
         }                                                                                   \
     } while (0)
+#define BAMD_REQUIRE(cond, msg) BAMD_REQUIRE_AS(__func__, cond, msg)
+// What an inference launch computes.  The kernel templates of fused.hip and fused64_infer.hpp take it as an int parameter with these values.
+enum InferKind : int { K_ENCODE = 0, K_DECODE = 1, K_FORWARD = 2 };
 
 // Tuning knobs are read on EVERY call (a getenv is nothing beside a launch; tests and A/B runs toggle them inside one process)
 inline long long env_ll(const char *name, long long dflt) {
@@ -90,6 +94,7 @@ struct bamd_handle {
     void *fpga_state = nullptr;     // FPGA_prototype_model shapes with ReLU (fpga.hip)
     void *pj_state = nullptr;       // PJ_Conv_AE handles (pjconv.hip; bamd_create_pjconv)
 
+    int param_dtype() const { return esize == 8 ? BAMD_F64 : BAMD_F32; }   // bamd_dtype of params, grads, m and v
     bool has_act(int l) const { return !(l == L / 2 - 1 || l == L - 1); }
     bool leaky() const { return act == BAMD_ACT_LEAKY_RELU; }   // the fused / fp64 / bf16 families implement LeakyReLU(0.01) only
 };
@@ -140,8 +145,8 @@ int generic_activation_means(bamd_handle *h, const void *x, int x_dtype, int64_t
 bool fpga_matches(const bamd_handle *h);         // the shape and activation of the family (whatever the mode)
 int fpga_setup(bamd_handle *h);                  // leaves h->fpga_state null for other shapes / modes or BALER_AMD_FORCE_GENERIC=1
 void fpga_teardown(bamd_handle *h);
-// kind: 0 = encode, 1 = decode (renorm / int_mask: un-normalise into a float64 output), 2 = forward + loss
-int fpga_infer(bamd_handle *h, int kind, const void *in, int in_dtype, int64_t n, const double *features, void *out, int out_dtype,
+// K_DECODE: renorm / int_mask un-normalise into a float64 output; K_FORWARD: loss_sum, `out` (the reconstruction) may be null
+int fpga_infer(bamd_handle *h, InferKind kind, const void *in, int in_dtype, int64_t n, const double *features, void *out, int out_dtype,
                const double *renorm, const uint8_t *int_mask, double *loss_sum, hipStream_t s);
 bool fpga_trains(const bamd_handle *h, int64_t n_rows);   // this training batch runs on fpga.hip (else: the layer-wise kernels)
 // fwd + loss + bwd (hp == nullptr), or the whole training step with Adam in the second launch; latent_grad may be null

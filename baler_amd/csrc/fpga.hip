@@ -171,7 +171,7 @@ struct Tiles {
     }
 };
 
-// kind 0: encode x -> z; 1: decode z -> out (optionally un-normalised); 2: forward + loss (recon may be null)
+// kind (an InferKind) K_ENCODE: x -> z; K_DECODE: z -> out (optionally un-normalised); K_FORWARD: forward + loss (recon may be null)
 template <typename T>
 __global__ void __launch_bounds__(NT) fpga_infer_k(int kind, int n, int z, const void *in, int in_f64, int64_t n_rows,
                                                    const double *features, const T *__restrict__ P, void *out, int out_f64,
@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(NT) fpga_infer_k(int kind, int n, int z, const
         const int64_t r0 = tile * RT;
         const int rows = (int)std::min<int64_t>(RT, n_rows - r0);
         __syncthreads();
-        if (kind == 1) {
+        if (kind == K_DECODE) {
             load_tile<T>(in, in_f64, r0, rows, z, nullptr, Y.y3);
         } else {
             load_tile<T>(in, in_f64, r0, rows, n, features, Y.y0);
@@ -198,7 +198,7 @@ __global__ void __launch_bounds__(NT) fpga_infer_k(int kind, int n, int z, const
             __syncthreads();
             fwd_layer<T, 2>(P, o, Y.y2, Y.y3);
         }
-        if (kind != 0) {
+        if (kind != K_ENCODE) {
             __syncthreads();
             fwd_layer<T, 3>(P, o, Y.y3, Y.y4);
             __syncthreads();
@@ -207,14 +207,14 @@ __global__ void __launch_bounds__(NT) fpga_infer_k(int kind, int n, int z, const
             fwd_layer<T, 5>(P, o, Y.y5, Y.y6);
         }
         __syncthreads();
-        if (kind == 2 && lane < rows)
+        if (kind == K_FORWARD && lane < rows)
             for (int k = threadIdx.x >> 6; k < n; k += NW) {
                 const T d = Y.y6[k * LD + lane] - Y.y0[k * LD + lane];
                 lsum += (double)d * (double)d;
             }
-        if (out) store_tile<T>(out, out_f64, r0, rows, kind == 0 ? z : n, kind == 1 ? renorm : nullptr, int_mask, kind == 0 ? Y.y3 : Y.y6);
+        if (out) store_tile<T>(out, out_f64, r0, rows, kind == K_ENCODE ? z : n, kind == K_DECODE ? renorm : nullptr, int_mask, kind == K_ENCODE ? Y.y3 : Y.y6);
     }
-    if (kind == 2) {
+    if (kind == K_FORWARD) {
         const double s = block_sum_nt(lsum, red);
         if (threadIdx.x == 0) loss_part[blockIdx.x] = s;
     }
@@ -357,13 +357,13 @@ int grid_for(const FpgaState *st, int64_t n_rows, size_t lds) {
 }
 
 template <typename T>
-int infer_T(bamd_handle *h, int kind, const void *in, int in_dtype, int64_t n_rows, const double *features, void *out, int out_dtype,
+int infer_T(bamd_handle *h, InferKind kind, const void *in, int in_dtype, int64_t n_rows, const double *features, void *out, int out_dtype,
             const double *renorm, const uint8_t *int_mask, double *loss_sum, hipStream_t s) {
     FpgaState *st = fst(h);
     const Layout o = make_layout(st->n, st->z);
     const size_t lds = infer_lds(o, sizeof(T));
     const int grid = grid_for(st, n_rows, lds);
-    if (kind == 2) {
+    if (kind == K_FORWARD) {
         if (int rc = st->lossp.ensure(sizeof(double) * grid)) return rc;
     }
     BAMD_HIP(hipFuncSetAttribute((const void *)fpga_infer_k<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -371,7 +371,7 @@ int infer_T(bamd_handle *h, int kind, const void *in, int in_dtype, int64_t n_ro
                        features, (const T *)h->params.p, out, out_dtype == BAMD_F64 ? 1 : 0, renorm, int_mask,
                        (double *)st->lossp.p);
     BAMD_HIP(hipGetLastError());
-    if (kind == 2) {
+    if (kind == K_FORWARD) {
         hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)st->lossp.p, grid, 1.0 / st->n,
                            loss_sum, 0);
         BAMD_HIP(hipGetLastError());
@@ -445,11 +445,11 @@ void fpga_teardown(bamd_handle *h) {
     h->fpga_state = nullptr;
 }
 
-int fpga_infer(bamd_handle *h, int kind, const void *in, int in_dtype, int64_t n, const double *features, void *out, int out_dtype,
+int fpga_infer(bamd_handle *h, InferKind kind, const void *in, int in_dtype, int64_t n, const double *features, void *out, int out_dtype,
                const double *renorm, const uint8_t *int_mask, double *loss_sum, hipStream_t s) {
     BAMD_REQUIRE(in_dtype == BAMD_F32 || in_dtype == BAMD_F64, "bad input dtype");
     BAMD_REQUIRE(!out || out_dtype == BAMD_F32 || out_dtype == BAMD_F64, "bad output dtype");
-    BAMD_REQUIRE(!(kind == 1 && renorm && out_dtype != BAMD_F64), "decode with features needs a float64 output");
+    BAMD_REQUIRE(!(kind == K_DECODE && renorm && out_dtype != BAMD_F64), "decode with features needs a float64 output");
     if (h->esize == 8) return infer_T<double>(h, kind, in, in_dtype, n, features, out, out_dtype, renorm, int_mask, loss_sum, s);
     return infer_T<float>(h, kind, in, in_dtype, n, features, out, out_dtype, renorm, int_mask, loss_sum, s);
 }

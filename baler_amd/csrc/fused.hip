@@ -521,7 +521,6 @@ __device__ __forceinline__ void store_rows(const v4 (&a)[tiles(D)], void *out, i
 }
 
 // ---- inference kernels: every wave streams 16-row tiles on its own ---------------------------------------
-enum { K_ENCODE = 0, K_DECODE = 1, K_FORWARD = 2 };
 
 template <class N>
 __device__ __forceinline__ void stage_bias(v4 *bias_lds, const v4 *packed) {
@@ -3913,7 +3912,7 @@ template <int F, int Z, bool RT = false> struct Impl {
                            N::slab_off(N::L), (const int *)st->slab_map.p, np, 1.0 / fr(h), (float *)grads);
         BAMD_HIP(hipGetLastError());
         if (tail_rows > 0) {
-            const char *xt = (const char *)x + (size_t)n * fr(h) * (x_dtype == BAMD_F64 ? 8 : 4);
+            const char *xt = (const char *)x + (size_t)n * fr(h) * dtype_bytes(x_dtype);
             return small_batch(h, xt, x_dtype, tail_rows, features, grads, nullptr, s, true);
         }
         return BAMD_OK;
@@ -4003,7 +4002,7 @@ template <int F, int Z, bool SMALL = true> struct ImplInferClass {
             const char *ce = getenv("BALER_AMD_CLASS_CHUNK_ROWS");      // (read per call: a training pass is milliseconds; tests toggle it)
             const int64_t chunk = ce ? atoll(ce) : 65536;
             if (chunk >= 16) {
-                const size_t row_bytes = (size_t)B::fr(h) * (x_dtype == BAMD_F64 ? 8 : 4);
+                const size_t row_bytes = (size_t)B::fr(h) * dtype_bytes(x_dtype);
                 const int64_t ck = chunk & ~(int64_t)15;
                 for (int64_t r0 = 0; r0 < n; r0 += ck) {
                     const int rc = B::small_batch(h, (const char *)x + (size_t)r0 * row_bytes, x_dtype, n - r0 < ck ? n - r0 : ck, features, grads,
@@ -4060,7 +4059,7 @@ template <int F, int Z, bool WRT = false> struct ImplWide {
     }
     static int encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype,
                       hipStream_t s) {
-        const size_t xes = x_dtype == BAMD_F64 ? 8 : 4, zes = z_dtype == BAMD_F64 ? 8 : 4;
+        const size_t xes = dtype_bytes(x_dtype), zes = dtype_bytes(z_dtype);
         const int fr = Fr(h), zr = Zr(h);
         for (int64_t r0 = 0; r0 < n; r0 += kChunkRows) {
             const int64_t rows = n - r0 < kChunkRows ? n - r0 : kChunkRows;
@@ -4100,7 +4099,7 @@ template <int F, int Z, bool WRT = false> struct ImplWide {
     }
     static int decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features, const uint8_t *int_mask,
                       void *out, int out_dtype, hipStream_t s) {
-        const size_t zes = z_dtype == BAMD_F64 ? 8 : 4, oes = out_dtype == BAMD_F64 ? 8 : 4;
+        const size_t zes = dtype_bytes(z_dtype), oes = dtype_bytes(out_dtype);
         if (features && out_dtype != BAMD_F64) { set_error("decode with features needs a float64 output"); return BAMD_ERR_INVALID; }
         const int fr = Fr(h), zr = Zr(h);
         for (int64_t r0 = 0; r0 < n; r0 += kChunkRows) {
@@ -4203,7 +4202,7 @@ template <int F, int Z, bool WRT = false> struct ImplWide {
     // normalise-on-load, as in encode)
     static int forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *recon, int recon_dtype,
                             double *loss_sum, hipStream_t s) {
-        const size_t xes = x_dtype == BAMD_F64 ? 8 : 4, oes = recon_dtype == BAMD_F64 ? 8 : 4;
+        const size_t xes = dtype_bytes(x_dtype), oes = dtype_bytes(recon_dtype);
         const int fr = Fr(h), zr = Zr(h);
         const int64_t chunk = 1 << 16;
         int rc = h->lossp.ensure(sizeof(double) * 4096 * ((n + chunk - 1) / chunk > 0 ? (n + chunk - 1) / chunk : 1));
@@ -4399,7 +4398,7 @@ template <int F, int Z> struct ImplWideBf16 {
                       hipStream_t s) {
         FusedState *st = state_of(h);
         if (st->wb_stale) { int rc = pack_extra(h, st, s); if (rc) return rc; }
-        const size_t xes = x_dtype == BAMD_F64 ? 8 : 4, zes = z_dtype == BAMD_F64 ? 8 : 4;
+        const size_t xes = dtype_bytes(x_dtype), zes = dtype_bytes(z_dtype);
         for (int64_t r0 = 0; r0 < n; r0 += W::kChunkRows) {
             const int64_t rows = n - r0 < W::kChunkRows ? n - r0 : W::kChunkRows;
             const void *src = (const char *)x + (size_t)r0 * F * xes;
@@ -4437,7 +4436,7 @@ template <int F, int Z> struct ImplWideBf16 {
                       void *out, int out_dtype, hipStream_t s) {
         FusedState *st = state_of(h);
         if (st->wb_stale) { int rc = pack_extra(h, st, s); if (rc) return rc; }
-        const size_t zes = z_dtype == BAMD_F64 ? 8 : 4, oes = out_dtype == BAMD_F64 ? 8 : 4;
+        const size_t zes = dtype_bytes(z_dtype), oes = dtype_bytes(out_dtype);
         if (features && out_dtype != BAMD_F64) { set_error("decode with features needs a float64 output"); return BAMD_ERR_INVALID; }
         for (int64_t r0 = 0; r0 < n; r0 += W::kChunkRows) {
             const int64_t rows = n - r0 < W::kChunkRows ? n - r0 : W::kChunkRows;

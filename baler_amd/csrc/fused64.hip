@@ -738,9 +738,9 @@ struct State64 {
 struct Ops64 {
     int (*setup)(bamd_handle *, State64 *);
     int (*step)(bamd_handle *, State64 *, const void *, int, int64_t, const double *, double *, const Adam64 *, hipStream_t);
-    // kind (I_ENCODE / I_DECODE / I_FORWARD), input, its dtype, rows, features applied to the input, output (+ dtype),
-    // un-normalisation of the output, int-column mask, loss sum (I_FORWARD)
-    int (*infer)(bamd_handle *, State64 *, int, const void *, int, int64_t, const double *, void *, int, const double *, const uint8_t *,
+    // kind (K_ENCODE / K_DECODE / K_FORWARD), input, its dtype, rows, features applied to the input, output (+ dtype),
+    // un-normalisation of the output, int-column mask, loss sum (K_FORWARD)
+    int (*infer)(bamd_handle *, State64 *, InferKind, const void *, int, int64_t, const double *, void *, int, const double *, const uint8_t *,
                  double *, hipStream_t);
 };
 State64 *st64(bamd_handle *h) { return (State64 *)h->fused64_state; }
@@ -940,7 +940,7 @@ template <int F, int Z, bool RT = false> struct Impl64 {
     }
     static int step(bamd_handle *h, State64 *st, const void *x, int x_dtype, int64_t n, const double *features, double *grads,
                     const Adam64 *ad, hipStream_t s) {
-        const size_t xes = x_dtype == BAMD_F64 ? 8 : 4;
+        const size_t xes = dtype_bytes(x_dtype);
         auto chain = [&](int k, int64_t r0, int64_t rows, int nblk, int64_t nblk_all, int nchunk) -> int {
             (void)k;
             int rc = BAMD_OK;
@@ -969,7 +969,7 @@ template <int F, int Z, bool RT = false> struct Impl64 {
         };
         return step64_common<N>(h, st, n, grads, ad, s, fr(h), chain);
     }
-    static int infer(bamd_handle *h, State64 *st, int kind, const void *x, int x_dtype, int64_t n, const double *features, void *out,
+    static int infer(bamd_handle *h, State64 *st, InferKind kind, const void *x, int x_dtype, int64_t n, const double *features, void *out,
                      int out_dtype, const double *renorm, const uint8_t *imask, double *loss_sum, hipStream_t s) {
         return fused64_infer_launch(F, Z, RT, h, (const double *)st->packed.p, kind, x, x_dtype, n, features, out, out_dtype, renorm, imask, loss_sum, s);
     }
@@ -1005,7 +1005,7 @@ template <int F, int FLO, int Z, int ZLO = 0> struct Impl64Q {
         const int64_t lim = env_ll("BALER_AMD_F64_QCHAIN_BLKS", -1);
         if (lim == 0) return BAMD_ERR_UNSUPPORTED;                                     // the caller runs the layer-wise kernels
         st->chunk_rows = (lim > 0 ? lim : 4096) * 16;
-        const size_t row_bytes = (size_t)h->dims[0] * (x_dtype == BAMD_F64 ? 8 : 4);
+        const size_t row_bytes = (size_t)h->dims[0] * dtype_bytes(x_dtype);
         auto chain = [&](int, int64_t r0, int64_t rows, int nblk, int64_t, int) -> int {
             const int rc = fused64q_launch(F, Z, true, 4u * (unsigned)nblk, s, (const double *)st->packed.p + (size_t)N::packed_d4() * 4,
                                            (const char *)x + (size_t)r0 * row_bytes, x_dtype == BAMD_F64, rows, features, (double *)st->imgs.p,
@@ -1016,7 +1016,7 @@ template <int F, int FLO, int Z, int ZLO = 0> struct Impl64Q {
     }
     // encode / decode / forward + loss: the register-chained inference kernel is generic in the tile counts (a wave owns every tile of its 16
     // rows); its instantiations for these classes live in fused64j.hip
-    static int infer(bamd_handle *h, State64 *st, int kind, const void *x, int x_dtype, int64_t n, const double *features, void *out,
+    static int infer(bamd_handle *h, State64 *st, InferKind kind, const void *x, int x_dtype, int64_t n, const double *features, void *out,
                      int out_dtype, const double *renorm, const uint8_t *imask, double *loss_sum, hipStream_t s) {
         return fused64_infer_launch(F, Z, true, h, (const double *)st->packed.p, kind, x, x_dtype, n, features, out, out_dtype, renorm, imask, loss_sum, s);
     }
@@ -1117,12 +1117,14 @@ int fused64_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const do
 
 
 // encode / decode / forward + loss of an F64 handle on the register-chained kernel (BAMD_ERR_UNSUPPORTED: no fp64 fused path for this
-// shape -> the caller falls back to the layer-wise kernels)
-int fused64_infer(bamd_handle *h, int kind, const void *x, int x_dtype, int64_t n, const double *features, void *out, int out_dtype,
+// shape or this call -> the caller falls back to the layer-wise kernels)
+int fused64_infer(bamd_handle *h, InferKind kind, const void *x, int x_dtype, int64_t n, const double *features, void *out, int out_dtype,
                   const double *renorm, const uint8_t *int_mask, double *loss_sum, hipStream_t s) {
     State64 *st = st64(h);
     static const bool on = !(getenv("BALER_AMD_F64_INFER") && getenv("BALER_AMD_F64_INFER")[0] == '0');
     if (!st || !on || n <= 0) return BAMD_ERR_UNSUPPORTED;
+    // the kernels load and store float32 / float64 latents, and un-normalise into float64 only (as renormalize_k)
+    if (kind == K_ENCODE ? !dtype_wide(out_dtype) : kind == K_DECODE && (!dtype_wide(x_dtype) || (renorm && out_dtype != BAMD_F64))) return BAMD_ERR_UNSUPPORTED;
     return st->ops->infer(h, st, kind, x, x_dtype, n, features, out, out_dtype, renorm, int_mask, loss_sum, s);
 }
 

@@ -16,7 +16,6 @@ namespace {
 // the activations in registers (the transposed register chain above with W = 1: a wave owns every tile of its rows, so there is no
 // exchange and no barrier), 4 waves per workgroup, persistent over row tiles.  A wave streams the half-model's fragments through
 // a ring that wraps across row tiles: 2 KiB per 4 MFMAs of 64 cycles = 8 B/clk per wave, far below the per-wave load rate.
-enum { I_ENCODE = 0, I_DECODE = 1, I_FORWARD = 2 };
 template <class N, int G0, int NGM, int D_> struct ISeq {      // GEMMs G0 .. G0 + NGM - 1 (forward fragments), one wave = all tiles
     static constexpr int D = D_;
     __host__ __device__ static constexpr int kd(int g) { return N::dim(G0 + g); }
@@ -113,7 +112,7 @@ __global__ void __launch_bounds__(256) infer64_kernel(const d4 *packed, const vo
                                                       const double *__restrict__ renorm, const uint8_t *__restrict__ imask,
                                                       double *__restrict__ loss_part, int fr, int zr) {
     using N = Net64<F, Z>;
-    constexpr int G0 = KIND == I_DECODE ? 4 : 0, NGM = KIND == I_FORWARD ? 8 : 4;
+    constexpr int G0 = KIND == K_DECODE ? 4 : 0, NGM = KIND == K_FORWARD ? 8 : 4;
     using SQ = ISeq<N, G0, NGM, 8>;
     constexpr int kNB = N::bf_off(N::L) - N::bf_off(0);
     extern __shared__ __attribute__((aligned(32))) unsigned char lds_raw[];
@@ -133,7 +132,7 @@ __global__ void __launch_bounds__(256) infer64_kernel(const d4 *packed, const vo
         asm volatile("" : "+v"(ws.voff));      // keep the fragment loads inside the loop (LICM would hoist the whole model)
         const int64_t row = tile * 16 + (lane & 15);
         const bool valid = row < n;
-        if constexpr (KIND == I_DECODE) {
+        if constexpr (KIND == K_DECODE) {
             d4 a4[tiles(Z)], s5[4], s6[7], s7[13], o8[tiles(F)];
             load_rows64<Z, RT>(a4, xin, in_f64, row, valid, lg, feats, zr);
             ilayer<N, SQ, 0, G0>(a4, s5, ring, ws, bias_lds, lg);
@@ -148,7 +147,7 @@ __global__ void __launch_bounds__(256) infer64_kernel(const d4 *packed, const vo
             ilayer<N, SQ, 1, G0>(s1, s2, ring, ws, bias_lds, lg);
             ilayer<N, SQ, 2, G0>(s2, s3, ring, ws, bias_lds, lg);
             ilayer<N, SQ, 3, G0>(s3, s4, ring, ws, bias_lds, lg);
-            if constexpr (KIND == I_ENCODE) {
+            if constexpr (KIND == K_ENCODE) {
                 store_rows64<Z, RT>(s4, out, out_f64, row, valid, lg, nullptr, nullptr, zr);
             } else {
                 d4 s5[4], s6[7], s7[13], o8[tiles(F)];
@@ -168,7 +167,7 @@ __global__ void __launch_bounds__(256) infer64_kernel(const d4 *packed, const vo
         }
         iseq_tail<SQ, SQ::real>(ring, ws, std::make_integer_sequence<int, SQ::total - SQ::real>{});      // step over the padding
     }
-    if constexpr (KIND == I_FORWARD) {      // per-workgroup loss partial, fixed order
+    if constexpr (KIND == K_FORWARD) {      // per-workgroup loss partial, fixed order
         const double wsum = block_sum_tree(lacc, red);
         if (threadIdx.x == 0) loss_part[blockIdx.x] = wsum;
     }
@@ -176,7 +175,7 @@ __global__ void __launch_bounds__(256) infer64_kernel(const d4 *packed, const vo
 
 // The launch of one shape (what Impl64::infer was): persistent grid, two workgroups per CU, the loss partials summed by a second launch
 template <int F, int Z, bool RT>
-int infer64_run(bamd_handle *h, const double *packed, int kind, const void *x, int x_dtype, int64_t n, const double *features, void *out,
+int infer64_run(bamd_handle *h, const double *packed, InferKind kind, const void *x, int x_dtype, int64_t n, const double *features, void *out,
                 int out_dtype, const double *renorm, const uint8_t *imask, double *loss_sum, hipStream_t s) {
     using N = Net64<F, Z>;
     const int fr = h->dims[0], zr = h->dims[4];
@@ -185,18 +184,18 @@ int infer64_run(bamd_handle *h, const double *packed, int kind, const void *x, i
     const int grid = (int)(ngroup < cap ? ngroup : cap);          // <= 256 registers: two workgroups per CU (two waves per SIMD), persistent
     constexpr int lds = (N::bf_off(N::L) - N::bf_off(0)) * 32;
     const int in64 = x_dtype == BAMD_F64, out64 = out_dtype == BAMD_F64;
-    if (kind == I_FORWARD) {
+    if (kind == K_FORWARD) {
         int rc = h->lossp.ensure(sizeof(double) * (size_t)(grid > 1024 ? grid : 1024));     // one partial per workgroup (BALER_AMD_F64_INFER_WGS may exceed 1024)
         if (rc) return rc;
     }
-    if (kind == I_ENCODE)
-        hipLaunchKernelGGL((infer64_kernel<F, Z, I_ENCODE, RT>), dim3(grid), dim3(256), lds, s, (const d4 *)packed, x, in64, n, features,
+    if (kind == K_ENCODE)
+        hipLaunchKernelGGL((infer64_kernel<F, Z, K_ENCODE, RT>), dim3(grid), dim3(256), lds, s, (const d4 *)packed, x, in64, n, features,
                            out, out64, renorm, imask, (double *)nullptr, fr, zr);
-    else if (kind == I_DECODE)
-        hipLaunchKernelGGL((infer64_kernel<F, Z, I_DECODE, RT>), dim3(grid), dim3(256), lds, s, (const d4 *)packed, x, in64, n, features,
+    else if (kind == K_DECODE)
+        hipLaunchKernelGGL((infer64_kernel<F, Z, K_DECODE, RT>), dim3(grid), dim3(256), lds, s, (const d4 *)packed, x, in64, n, features,
                            out, out64, renorm, imask, (double *)nullptr, fr, zr);
     else {
-        hipLaunchKernelGGL((infer64_kernel<F, Z, I_FORWARD, RT>), dim3(grid), dim3(256), lds, s, (const d4 *)packed, x, in64, n, features,
+        hipLaunchKernelGGL((infer64_kernel<F, Z, K_FORWARD, RT>), dim3(grid), dim3(256), lds, s, (const d4 *)packed, x, in64, n, features,
                            out, out64, renorm, imask, (double *)h->lossp.p, fr, zr);
         hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, grid, 1.0 / fr, loss_sum, 0);
     }

@@ -77,13 +77,13 @@ template <int NL> __device__ __forceinline__ void lrelu(d4 (&a)[NL]) {
         for (int r = 0; r < 4; ++r) a[i][r] = a[i][r] > 0.0 ? a[i][r] : a[i][r] * kSlope;
 }}  // namespace
 
-// fused64i.hip / fused64j.hip: infer64_kernel<F, Z, KIND, RT> (encode / decode / forward + loss of an fp64 handle; kind: 0 / 1 / 2) for the
+// fused64i.hip / fused64j.hip: infer64_kernel<F, Z, KIND, RT> (encode / decode / forward + loss of an fp64 handle; KIND: an InferKind) for the
 // shapes of find64 -- the exact 24-column latents and the classes up to 63 columns in fused64i.hip, the 64 .. 127-column / latent <= 63
 // classes in fused64j.hip (two translation units: 69 fully unrolled kernels would take six minutes in one); BAMD_ERR_UNSUPPORTED for others
-int fused64_infer_launch(int F, int Z, bool rt, bamd_handle *h, const double *packed, int kind, const void *x, int x_dtype, int64_t n,
+int fused64_infer_launch(int F, int Z, bool rt, bamd_handle *h, const double *packed, InferKind kind, const void *x, int x_dtype, int64_t n,
                          const double *features, void *out, int out_dtype, const double *renorm, const uint8_t *imask, double *loss_sum,
                          hipStream_t s);
-int fused64j_infer_launch(int F, int Z, bool rt, bamd_handle *h, const double *packed, int kind, const void *x, int x_dtype, int64_t n,
+int fused64j_infer_launch(int F, int Z, bool rt, bamd_handle *h, const double *packed, InferKind kind, const void *x, int x_dtype, int64_t n,
                           const double *features, void *out, int out_dtype, const double *renorm, const uint8_t *imask, double *loss_sum,
                           hipStream_t s);
 // fused64q.hip: chain64q_kernel<F, Z, RT> for the shapes fused64.hip instantiates; BAMD_ERR_UNSUPPORTED for any other (F, Z, RT)

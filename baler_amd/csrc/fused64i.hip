@@ -3,7 +3,7 @@
 
 namespace bamd {
 
-int fused64_infer_launch(int F, int Z, bool rt, bamd_handle *h, const double *packed, int kind, const void *x, int x_dtype, int64_t n,
+int fused64_infer_launch(int F, int Z, bool rt, bamd_handle *h, const double *packed, InferKind kind, const void *x, int x_dtype, int64_t n,
                          const double *features, void *out, int out_dtype, const double *renorm, const uint8_t *imask, double *loss_sum,
                          hipStream_t s) {
 #define I_CASE(F_, Z_, RT_) if (F == F_ && Z == Z_ && rt == RT_) return infer64_run<F_, Z_, RT_>(h, packed, kind, x, x_dtype, n, features, out, out_dtype, renorm, imask, loss_sum, s);

@@ -1184,7 +1184,7 @@ static int forward_loss_T(bamd_handle *h, const void *x, int x_dtype, int64_t n,
     int c = h->dims[0];
     rc = h->lossp.ensure(sizeof(double) * 1024);
     if (rc) return rc;
-    size_t oes = recon_dtype == BAMD_F64 ? 8 : 4;
+    size_t oes = dtype_bytes(recon_dtype);
     int chunk_i = 0;
     for (int64_t r0 = 0; r0 < n; r0 += wk.chunk, ++chunk_i) {
         int64_t rows = n - r0 < wk.chunk ? n - r0 : wk.chunk;

@@ -514,7 +514,7 @@ int pj_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const doubl
     const int64_t G = std::min<int64_t>(n, kInferGroup);
     PJ_TRY(ensure_ws(h, G, false));
     const Bufs B = carve((float *)st->ws.p, G, st->z, false);
-    const size_t xb = x_dtype == BAMD_F64 ? 8 : 4;
+    const size_t xb = dtype_bytes(x_dtype);
     for (int64_t r0 = 0; r0 < n; r0 += G) {
         const int nb = (int)std::min<int64_t>(G, n - r0);
         const float *xin = nullptr;
@@ -535,7 +535,7 @@ int pj_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const doubl
     const int64_t G = std::min<int64_t>(n, kInferGroup);
     PJ_TRY(ensure_ws(h, G, false));
     const Bufs B = carve((float *)st->ws.p, G, st->z, false);
-    const size_t ob = out_dtype == BAMD_F64 ? 8 : 4;
+    const size_t ob = dtype_bytes(out_dtype);
     for (int64_t r0 = 0; r0 < n; r0 += G) {
         const int nb = (int)std::min<int64_t>(G, n - r0);
         const float *zin = (const float *)z + r0 * st->z;
@@ -560,7 +560,7 @@ int pj_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const
     int64_t nparts = 0;
     for (int64_t r0 = 0; r0 < n; r0 += G) nparts += dec5_blocks(std::min<int64_t>(G, n - r0));
     PJ_TRY(st->lossp.ensure((size_t)nparts * sizeof(double)));
-    const size_t xb = x_dtype == BAMD_F64 ? 8 : 4, rb = recon_dtype == BAMD_F64 ? 8 : 4;
+    const size_t xb = dtype_bytes(x_dtype), rb = dtype_bytes(recon_dtype);
     int64_t part = 0;
     for (int64_t r0 = 0; r0 < n; r0 += G) {
         const int nb = (int)std::min<int64_t>(G, n - r0);
@@ -594,7 +594,7 @@ int pj_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double 
     int64_t nparts = 0;
     for (int64_t r0 = 0; r0 < n; r0 += G) nparts += dec5_blocks(std::min<int64_t>(G, n - r0));
     PJ_TRY(st->lossp.ensure((size_t)nparts * sizeof(double)));
-    const size_t xb = x_dtype == BAMD_F64 ? 8 : 4;
+    const size_t xb = dtype_bytes(x_dtype);
     int64_t part = 0, gi = 0;
     for (int64_t r0 = 0; r0 < n; r0 += G, ++gi) {
         const int nb = (int)std::min<int64_t>(G, n - r0);

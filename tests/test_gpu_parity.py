@@ -1369,6 +1369,48 @@ def test_train_step_under_routing_knobs(case, monkeypatch):
     assert rel_l2(orc.encode(dims, p0, x), z_new) > 5e-2       # ... by far more than the tolerance the encode is held to
 
 
+_ROUTE_THRESHOLDS = {
+    # handle: dims, mode, activation, (knob, value) that brings the threshold down to a few rows, last row count below it
+    "bf16-small-rows": (orc.ae_dims(24, 15), "bf16", "leaky_relu", ("BALER_AMD_BF16_SMALL_ROWS", "64"), 64),   # read per call
+    "fpga-f32-rows": ([24, 20, 10, 15, 10, 20, 24], "fp32", "relu", None, 8192),                               # a constant of fpga.hip
+    "two-state-latency": (orc.ae_dims(80, 16), "fp32", "leaky_relu", ("BALER_AMD_LATENCY_ROWS", "64"), 64),    # read at bamd_create
+}
+
+
+@pytest.mark.parametrize("above", [False, True], ids=["last-below", "first-above"])
+@pytest.mark.parametrize("case", list(_ROUTE_THRESHOLDS))
+def test_train_route_agrees_at_every_row_threshold(case, above, monkeypatch):
+    """bamd_train_step and bamd_fwd_bwd read ONE training route (api.hip: train_family), so at the row counts either side of every
+    threshold at which that route, or a family's decline behind it, changes kernels the one-call step == bamd_fwd_bwd + bamd_adam_step
+    bit for bit: a BF16 handle (fp32 small-batch kernels up to BALER_AMD_BF16_SMALL_ROWS rows, the bf16 pair above), an fp32
+    FPGA_prototype_model handle (fused up to 8,192 rows, layer-wise above) and a two-state 64..127-column handle (small-batch class up to
+    BALER_AMD_LATENCY_ROWS rows, the wide launches above).  The fp32 AE(24, 15) handle's BALER_AMD_LATENCY_ROWS threshold is straddled
+    with the same bit equalities by test_train_step_equals_fwd_bwd_then_adam (5,000 and 20,000 rows around 12,288)."""
+    dims, mode, act, knob, rows = _ROUTE_THRESHOLDS[case]
+    if knob:
+        monkeypatch.setenv(*knob)
+    n = rows + 1 if above else rows
+    p0 = orc.formula_params(dims, 23)
+    xd = dev(np.random.default_rng(n).random((n, dims[0])), torch.float32)
+    runs = []
+    for one_call in (False, True):
+        h = native.Handle(dims, mode, act=act)
+        flat = dev(np.concatenate([p0, [0.0]]), torch.float32)
+        h.load_params(flat)
+        m, v, grads = torch.zeros_like(flat), torch.zeros_like(flat), torch.zeros_like(flat)
+        for t in range(1, 4):
+            if one_call:
+                h.train_step(xd, flat, m, v, t, 1e-2, grads=grads if t % 2 else None)
+            else:
+                h.fwd_bwd(xd, grads)
+                h.adam_step(flat, grads, m, v, t, 1e-2)
+        runs.append((flat.clone(), m.clone(), v.clone(), h.encode(xd, out_dtype=torch.float32)))
+        h.close()
+    for a, b in zip(runs[0], runs[1]):
+        assert torch.equal(a, b)
+    assert np.abs(runs[1][0][:-1].double().cpu().numpy() - p0).max() > 5e-3          # three steps of lr 1e-2 moved the parameters
+
+
 @pytest.mark.parametrize("dims,path", [(orc.ae_dims(100, 10), "fused"), (orc.ae_dims(900, 9), "fused"), (orc.ae_dims(30, 7), "fused"),
                                        ([400, 120, 60, 30, 9, 30, 60, 120, 400], "generic")])
 def test_bf16_mode_of_a_shape_without_bf16_kernels_runs_in_fp32(dims, path, capfd):
