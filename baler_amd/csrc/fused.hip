@@ -2492,6 +2492,33 @@ __device__ __forceinline__ void q_write_x(float *__restrict__ q, const v4 (&a)[t
     }
 }
 
+// dZ = dY * lrelu'(y) with y read back from the X^T image of dimension D that this wave has just written (q_write_x<D>: the wave's own
+// stores, so no barrier in between).  The activation's registers are then free while the layer's dX chain runs: the chain role of
+// the role-split pair needs that to stay inside 256 registers.  The ones slot holds 1.0 where the padded activation was 0: slope 0.01.
+template <int D>
+__device__ __forceinline__ void lrelu_bwd_img(v4 (&d)[tiles(D)], const float *__restrict__ q, int lane, int wave) {
+    constexpr int T = tiles(D) - 1, V = D - 16 * T, R1 = V / 4, G1 = V % 4;
+    typedef const float __attribute__((address_space(3))) *lds_cf;
+    const int col = 16 * wave + (lane & 15), g = lane >> 4;
+    lds_cf p[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        p[r] = (lds_cf)q + ((4 * g + r) * kQS + col);
+        asm volatile("" : "+v"(p[r]));
+    }
+#pragma unroll
+    for (int t = 0; t < tiles(D); ++t) {
+        v4 sl;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float y = p[r][t * 16 * kQS];
+            if (t == T && r == R1) y = g == G1 ? 0.f : y;
+            sl[r] = y > 0.f ? 1.0f : 0.01f;
+        }
+        d[t] = d[t] * sl;
+    }
+}
+
 template <class N, int l> struct DW {
     static constexpr int NT = tiles(N::dim(l + 1)), KT = tiles(N::dim(l) + 1), TOT = NT * KT, T = (TOT + 3) / 4;
     static constexpr int rows_x = 16 * KT, rows_dz = 16 * NT;   // image rows
@@ -2851,6 +2878,213 @@ __global__ void __launch_bounds__(256) train_enc_kernel(const v4 *packed, const 
     dw_flush<N, 1>(slab, g1, lane, wave); dw_flush<N, 0>(slab, g0, lane, wave);
 }
 
+#endif
+
+#if BAMD_SPLIT == 2
+// ---- the training pair split by ROLE: 512 threads, two waves per SIMD ---------------------------------------------------------
+// The pair above runs one wave per SIMD, and everything that wave issues beside its MFMAs (LeakyReLU, the image writes, fragment
+// reads, barriers) adds to the MFMA time.  Here waves 0..3 are CHAIN waves (rows, forward, loss, image writes, the dX chain: the
+// activation stash and the d arrays, no accumulators) and waves 4..7 WEIGHT-GRADIENT waves (dw_phase / dw_flush only: the
+// accumulators and two fragment buffers), so that each SIMD has a second wave to issue from.  Same images, same A/B alternation,
+// one barrier per layer across the eight waves: after barrier k the weight-gradient waves read layer l's images while the chain
+// waves write layer l - 1's into the other buffer, which was last read one barrier earlier.  The number of layers per iteration is
+// even in both kernels, so the alternation runs on across iterations and the last dw_phase of a row group runs beside the forward
+// of the next one.  Both roles execute the same barriers: one per layer and iteration, then those of the loss tree.
+// Tiles are dealt by (wave - 4) exactly as the pair above deals them by wave, every tile sums the same rows in the same order and
+// the loss tree runs over the same 256 chain lanes: results are bit-identical to the pair above.
+template <int F, int Z, bool RT = false>
+__global__ void __launch_bounds__(512) train_dec_roles_kernel(const v4 *packed, const void *__restrict__ xin, int in_f64,
+                                                              int64_t n, const double *__restrict__ feats, v4 *__restrict__ slabs,
+                                                              v4 *__restrict__ dz_out, int fr, int zr) {
+    using N = Net<F, Z>;
+    using S = StreamTrainDec<N>;
+    constexpr int kImgA = img_a_rows<N>();
+    static_assert(DW<N, 7>::rows_x + DW<N, 7>::rows_dz <= kImgA && DW<N, 6>::rows_x + DW<N, 6>::rows_dz <= kImgB &&
+                  DW<N, 5>::rows_x + DW<N, 5>::rows_dz <= kImgA && DW<N, 4>::rows_x + DW<N, 4>::rows_dz <= kImgB &&
+                  DW<N, 3>::rows_x + DW<N, 3>::rows_dz <= kImgA && DW<N, 2>::rows_x + DW<N, 2>::rows_dz <= kImgB, "image buffers");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *imgA = lds, *imgB = lds + kImgA * kQS;
+    const v4 *bias_lds = packed + N::bf_off(0);
+    if constexpr (train_bias_in_lds<N>()) {
+        v4 *stage = (v4 *)(lds + (kImgA + kImgB) * kQS);
+        stage_bias<N>(stage, packed);
+        bias_lds = stage;
+    }
+    int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t ngroups = (n + kRowsPerWG - 1) / kRowsPerWG;
+    double lacc = 0.0;
+    if (wave >= 4) {
+        int tw = wave - 4;                             // the wave index of the tile dealing
+        v4 *slab = slabs + (int64_t)blockIdx.x * 64;   // column of this workgroup in the [tile][workgroup][lane] buffer
+        v4 g7[DW<N, 7>::T], g6[DW<N, 6>::T], g5[DW<N, 5>::T], g4[DW<N, 4>::T], g3[DW<N, 3>::T], g2[DW<N, 2>::T];
+        zero_tiles(g7); zero_tiles(g6); zero_tiles(g5); zero_tiles(g4); zero_tiles(g3); zero_tiles(g2);
+        for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+            asm volatile("" : "+s"(tw), "+v"(lane));   // see train_dec_kernel
+            __syncthreads();
+            dw_phase<N, 7>(imgA + DW<N, 7>::rows_x * kQS, imgA, g7, lane, tw);
+            __syncthreads();
+            dw_phase<N, 6>(imgB + DW<N, 6>::rows_x * kQS, imgB, g6, lane, tw);
+            __syncthreads();
+            dw_phase<N, 5>(imgA + DW<N, 5>::rows_x * kQS, imgA, g5, lane, tw);
+            __syncthreads();
+            dw_phase<N, 4>(imgB + DW<N, 4>::rows_x * kQS, imgB, g4, lane, tw);
+            __syncthreads();
+            dw_phase<N, 3>(imgA + DW<N, 3>::rows_x * kQS, imgA, g3, lane, tw);
+            __syncthreads();
+            dw_phase<N, 2>(imgB + DW<N, 2>::rows_x * kQS, imgB, g2, lane, tw);
+        }
+        dw_flush<N, 7>(slab, g7, lane, tw); dw_flush<N, 6>(slab, g6, lane, tw);
+        dw_flush<N, 5>(slab, g5, lane, tw); dw_flush<N, 4>(slab, g4, lane, tw);
+        dw_flush<N, 3>(slab, g3, lane, tw); dw_flush<N, 2>(slab, g2, lane, tw);
+    } else {
+        WStream ws = make_stream(packed + S::start_f4, (N::packed_f4() - S::start_f4) * 16, lane);
+        Ring ring;
+        ring_prime<S::total>(ring, ws);
+        v4 a0n[tiles(F)];   // next row group's input, loaded one iteration ahead (software pipeline)
+        {
+            const int64_t row0 = (int64_t)blockIdx.x * kRowsPerWG + 16 * wave + (lane & 15);
+            load_rows<F, RT>(a0n, xin, in_f64, row0, row0 < n, lane, feats, fr);
+        }
+        for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+            asm volatile("" : "+v"(ws.voff), "+s"(wave), "+v"(lane));   // see train_dec_kernel
+            const int64_t row = grp * kRowsPerWG + 16 * wave + (lane & 15);
+            const bool valid = row < n;
+            const int64_t row_next = row + (int64_t)gridDim.x * kRowsPerWG;
+            const bool valid_next = row_next < n;
+            RawRows<F> xraw;
+            v4 a2[7], a3[4], a4[tiles(Z)], a5[4], a6[7], a7[13], d8[tiles(F)];
+            {
+                v4 a0[tiles(F)], a1[13];
+#pragma unroll
+                for (int t = 0; t < tiles(F); ++t) a0[t] = a0n[t];
+                fwd_layer<N, S, 0>(a0, a1, ring, ws, bias_lds, lane);
+                fwd_layer<N, S, 1>(a1, a2, ring, ws, bias_lds, lane);
+                fwd_layer<N, S, 2>(a2, a3, ring, ws, bias_lds, lane);
+                fwd_layer<N, S, 3>(a3, a4, ring, ws, bias_lds, lane);
+                fwd_layer<N, S, 4>(a4, a5, ring, ws, bias_lds, lane);
+                fwd_layer<N, S, 5>(a5, a6, ring, ws, bias_lds, lane);
+                fwd_layer<N, S, 6>(a6, a7, ring, ws, bias_lds, lane);
+                fwd_layer<N, S, 7>(a7, d8, ring, ws, bias_lds, lane);
+                // loss and dL/drecon = 2 (r - x)/C  (utils.py:195-199); invalid rows contribute nothing
+#pragma unroll
+                for (int t = 0; t < tiles(F); ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float d = d8[t][r] - a0[t][r];
+                        const bool live = valid && slot_feature(F, t, lane >> 4, r) >= 0;
+                        if (live) lacc += (double)d * (double)d;
+                        d8[t][r] = live ? d * (2.0f / (float)(RT ? fr : F)) : 0.f;
+                    }
+            }
+            // per layer: image writes -> dX chain (registers only) -> barrier; the weight-gradient waves take the images from there
+            v4 d7[13], d6[7], d5[4], d4[tiles(Z)], d3[4], d2[7];
+            q_write_x<200>(imgA, a7, lane, wave); q_write(imgA + DW<N, 7>::rows_x * kQS, d8, lane, wave);
+            bwd_layer<N, S, 7>(d8, d7, ring, ws); lrelu_bwd_img<200>(d7, imgA, lane, wave);   // a7 is dead from its image write on
+            __syncthreads();
+
+            q_write_x<100>(imgB, a6, lane, wave); q_write(imgB + DW<N, 6>::rows_x * kQS, d7, lane, wave);
+            bwd_layer<N, S, 6>(d7, d6, ring, ws); lrelu_bwd(d6, a6);
+            __syncthreads();
+            load_rows_issue<F, RT>(xraw, xin, in_f64, row_next, valid_next, lane, fr);   // behind the register peak; lands during layer 5
+
+            q_write_x<50>(imgA, a5, lane, wave); q_write(imgA + DW<N, 5>::rows_x * kQS, d6, lane, wave);
+            bwd_layer<N, S, 5>(d6, d5, ring, ws); lrelu_bwd(d5, a5);
+            __syncthreads();
+            load_rows_finish<F, RT>(a0n, xraw, valid_next, lane, feats, fr);
+
+            q_write_x<Z>(imgB, a4, lane, wave); q_write(imgB + DW<N, 4>::rows_x * kQS, d5, lane, wave);
+            bwd_layer<N, S, 4>(d5, d4, ring, ws);            // en4 has no activation: dL/dz
+            __syncthreads();
+
+            q_write_x<50>(imgA, a3, lane, wave); q_write(imgA + DW<N, 3>::rows_x * kQS, d4, lane, wave);
+            bwd_layer<N, S, 3>(d4, d3, ring, ws); lrelu_bwd(d3, a3);
+            __syncthreads();
+
+            q_write_x<100>(imgB, a2, lane, wave); q_write(imgB + DW<N, 2>::rows_x * kQS, d3, lane, wave);
+            bwd_layer<N, S, 2>(d3, d2, ring, ws); lrelu_bwd(d2, a2);
+            // dZ_1 hand-off, see train_dec_kernel
+#pragma unroll
+            for (int t = 0; t < 7; ++t) dz_out[((row >> 4) * 7 + t) * 64 + lane] = d2[t];
+            __syncthreads();
+            ring_tail<S::total>(ring, ws);
+        }
+    }
+    // per-workgroup loss partial: the fixed-order tree over threads 0..255, the chain lanes (the weight-gradient waves only keep
+    // the barriers company: their slots 256..511 are never read)
+    __syncthreads();
+    const double wsum = block_sum_tree(lacc, (double *)lds);
+    if (threadIdx.x == 0) ((double *)(slabs + (int64_t)N::slab_off(N::L) * gridDim.x * 64))[blockIdx.x] = wsum;   // loss partials after the tiles
+}
+
+template <int F, int Z, bool RT = false>
+__global__ void __launch_bounds__(512) train_enc_roles_kernel(const v4 *packed, const void *__restrict__ xin, int in_f64,
+                                                              int64_t n, const double *__restrict__ feats, v4 *__restrict__ slabs,
+                                                              const v4 *__restrict__ dz_in, int fr, int zr) {
+    using N = Net<F, Z>;
+    using S = StreamTrainEnc<N>;
+    constexpr int kImgA = img_a_rows<N>();
+    static_assert(DW<N, 1>::rows_x + DW<N, 1>::rows_dz <= kImgB && DW<N, 0>::rows_x + DW<N, 0>::rows_dz <= kImgA, "image buffers");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *imgA = lds, *imgB = lds + kImgA * kQS;
+    const v4 *bias_lds = packed + N::bf_off(0);
+    if constexpr (train_bias_in_lds<N>()) {
+        v4 *stage = (v4 *)(lds + (kImgA + kImgB) * kQS);
+        stage_bias<N>(stage, packed);
+        bias_lds = stage;
+    }
+    int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t ngroups = (n + kRowsPerWG - 1) / kRowsPerWG;
+    if (wave >= 4) {
+        int tw = wave - 4;
+        v4 *slab = slabs + (int64_t)blockIdx.x * 64;
+        v4 g1[DW<N, 1>::T], g0[DW<N, 0>::T];
+        zero_tiles(g1); zero_tiles(g0);
+        for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+            asm volatile("" : "+s"(tw), "+v"(lane));   // see train_dec_kernel
+            __syncthreads();
+            dw_phase<N, 1>(imgB + DW<N, 1>::rows_x * kQS, imgB, g1, lane, tw);
+            __syncthreads();
+            dw_phase<N, 0>(imgA + DW<N, 0>::rows_x * kQS, imgA, g0, lane, tw);
+        }
+        dw_flush<N, 1>(slab, g1, lane, tw); dw_flush<N, 0>(slab, g0, lane, tw);
+    } else {
+        WStream ws = make_stream(packed + S::start_f4, (N::packed_f4() - S::start_f4) * 16, lane);
+        Ring ring;
+        ring_prime<S::total>(ring, ws);
+        v4 a0n[tiles(F)], d2n[7];   // next row group's inputs, loaded one iteration ahead (software pipeline)
+        {
+            const int64_t row0 = (int64_t)blockIdx.x * kRowsPerWG + 16 * wave + (lane & 15);
+            load_rows<F, RT>(a0n, xin, in_f64, row0, row0 < n, lane, feats, fr);
+#pragma unroll
+            for (int t = 0; t < 7; ++t) d2n[t] = dz_in[((row0 >> 4) * 7 + t) * 64 + lane];
+        }
+        for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+            asm volatile("" : "+v"(ws.voff), "+s"(wave), "+v"(lane));   // see train_dec_kernel
+            const int64_t row = grp * kRowsPerWG + 16 * wave + (lane & 15);
+            const int64_t row_next = row + (int64_t)gridDim.x * kRowsPerWG;
+            const bool valid_next = row_next < n;
+            RawRows<F> xraw;
+            v4 a0[tiles(F)], a1[13], d2[7], d1[13];
+#pragma unroll
+            for (int t = 0; t < tiles(F); ++t) a0[t] = a0n[t];
+#pragma unroll
+            for (int t = 0; t < 7; ++t) d2[t] = d2n[t];
+            fwd_layer<N, S, 0>(a0, a1, ring, ws, bias_lds, lane);
+
+            q_write_x<200>(imgB, a1, lane, wave); q_write(imgB + DW<N, 1>::rows_x * kQS, d2, lane, wave);
+            bwd_layer<N, S, 1>(d2, d1, ring, ws); lrelu_bwd(d1, a1);
+            __syncthreads();
+            load_rows_issue<F, RT>(xraw, xin, in_f64, row_next, valid_next, lane, fr);   // lands while the long dW phase holds the next barrier
+#pragma unroll
+            for (int t = 0; t < 7; ++t) d2n[t] = dz_in[((row_next >> 4) * 7 + t) * 64 + lane];   // one round past the end stays inside the buffer
+
+            q_write_x<F>(imgA, a0, lane, wave); q_write(imgA + DW<N, 0>::rows_x * kQS, d1, lane, wave);
+            __syncthreads();
+            load_rows_finish<F, RT>(a0n, xraw, valid_next, lane, feats, fr);
+            ring_tail<S::total>(ring, ws);
+        }
+    }
+}
 #endif
 
 // ---- small-batch kernels (the reference's batch_size = 512 regime; used up to FusedState::latency_max_rows) -------
@@ -3813,6 +4047,10 @@ static int infer_grid(int64_t n) {
     return (int)(wg < 1 ? 1 : (wg > 1024 ? 1024 : wg));
 }
 
+// which training pair fwd_bwd launches where an instantiation has both (BALER_AMD_TRAIN_ROLES overrides it per call): the role-split
+// pair, 1.7 % ahead at 1M rows
+constexpr int kTrainRolesDefault = 1;
+
 // RT = true: the instantiation serves a CLASS of narrow tables -- every AE(f, z) with f <= F, z <= Z and the
 // reference's hidden widths (models.py:122-139 builds AE(n_features, z_dim) for ANY column count, baler.py:117-123 derives any latent):
 // F = 16 T - 1 is the class width, the real widths are kernel arguments (load_rows / store_rows, RT), the pack / gradient maps leave
@@ -3831,6 +4069,8 @@ template <int F, int Z, bool RT = false> struct Impl {
         return true;
     }
     static constexpr int train_lds = (img_a_rows<N>() + kImgB) * kQS * (int)sizeof(float) + (train_bias_in_lds<N>() ? (N::bf_off(8) - N::bf_off(0)) * 16 : 0);      // images (+ bias fragments)
+    // the role-split pair needs its chain role inside 256 registers: the two-tile inputs (the 24-column models, the 31-column class)
+    static constexpr bool train_roles = kSplit == 2 && !RT && tiles(F) <= 2;
     static int fr(const bamd_handle *h) { return h->dims[0]; }
     static int zr(const bamd_handle *h) { return h->dims[4]; }
     static int setup(bamd_handle *h, FusedState *st) {
@@ -3840,6 +4080,10 @@ template <int F, int Z, bool RT = false> struct Impl {
         if (rc) return rc;
         BAMD_HIP(hipFuncSetAttribute((const void *)train_dec_kernel<F, Z, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, train_lds));
         BAMD_HIP(hipFuncSetAttribute((const void *)train_enc_kernel<F, Z, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, train_lds));
+        if constexpr (train_roles) {
+            BAMD_HIP(hipFuncSetAttribute((const void *)train_dec_roles_kernel<F, Z, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, train_lds));
+            BAMD_HIP(hipFuncSetAttribute((const void *)train_enc_roles_kernel<F, Z, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, train_lds));
+        }
         return BAMD_OK;
     }
     static int encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype,
@@ -3904,10 +4148,23 @@ template <int F, int Z, bool RT = false> struct Impl {
         // whole row groups + one round of prefetch overrun (the second kernel loads the next group's record unconditionally)
         rc = st->dz.ensure((size_t)(ngroups + grid) * kRowsPerWG * (kSplit == 2 ? 7 * 64 : 64));
         if (rc) return rc;
-        hipLaunchKernelGGL((train_dec_kernel<F, Z, RT>), dim3(grid), dim3(256), train_lds, s, (const v4 *)h->packed.p, x,
-                           x_dtype == BAMD_F64, n, features, (v4 *)h->slabs.p, (v4 *)st->dz.p, fr(h), zr(h));
-        hipLaunchKernelGGL((train_enc_kernel<F, Z, RT>), dim3(grid), dim3(256), train_lds, s, (const v4 *)h->packed.p, x,
-                           x_dtype == BAMD_F64, n, features, (v4 *)h->slabs.p, (const v4 *)st->dz.p, fr(h), zr(h));
+        // BALER_AMD_TRAIN_ROLES (read per call: tests and A/B measurements toggle it): 1 = the role-split pair (two waves per SIMD),
+        // 0 = the one-wave pair; the same grid, LDS, slabs and hand-off, bit-identical results
+        bool roles = false;
+        if constexpr (train_roles) roles = env_ll("BALER_AMD_TRAIN_ROLES", kTrainRolesDefault) != 0;
+        if (roles) {
+            if constexpr (train_roles) {
+                hipLaunchKernelGGL((train_dec_roles_kernel<F, Z, RT>), dim3(grid), dim3(512), train_lds, s, (const v4 *)h->packed.p, x,
+                                   x_dtype == BAMD_F64, n, features, (v4 *)h->slabs.p, (v4 *)st->dz.p, fr(h), zr(h));
+                hipLaunchKernelGGL((train_enc_roles_kernel<F, Z, RT>), dim3(grid), dim3(512), train_lds, s, (const v4 *)h->packed.p, x,
+                                   x_dtype == BAMD_F64, n, features, (v4 *)h->slabs.p, (const v4 *)st->dz.p, fr(h), zr(h));
+            }
+        } else {
+            hipLaunchKernelGGL((train_dec_kernel<F, Z, RT>), dim3(grid), dim3(256), train_lds, s, (const v4 *)h->packed.p, x,
+                               x_dtype == BAMD_F64, n, features, (v4 *)h->slabs.p, (v4 *)st->dz.p, fr(h), zr(h));
+            hipLaunchKernelGGL((train_enc_kernel<F, Z, RT>), dim3(grid), dim3(256), train_lds, s, (const v4 *)h->packed.p, x,
+                               x_dtype == BAMD_F64, n, features, (v4 *)h->slabs.p, (const v4 *)st->dz.p, fr(h), zr(h));
+        }
         hipLaunchKernelGGL(reduce_slabs_k<float>, dim3(N::slab_off(N::L) + 1), dim3(256), 0, s, (const v4 *)h->slabs.p, grid,
                            N::slab_off(N::L), (const int *)st->slab_map.p, np, 1.0 / fr(h), (float *)grads);
         BAMD_HIP(hipGetLastError());
