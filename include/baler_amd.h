@@ -15,6 +15,8 @@
  *    the library borrows the pointers for the duration of the call and owns only its handle
  *    (layer descriptor, MFMA-fragment-packed weight copy, partial-gradient slabs, activation
  *    workspace);
+ *  - every pointer argument needs the alignment of its element type and nothing more (a row block of a larger allocation
+ *    is a valid argument), and a call reads and writes nothing outside the rows, codes and parameters it was given;
  *  - all work is enqueued asynchronously on the hipStream_t passed as `stream` (void*; NULL =
  *    the default stream); nothing synchronises the host;
  *  - one handle per (model, device); a handle is not thread-safe, and it is SINGLE-STREAM: the library re-packs its
