@@ -1,4 +1,5 @@
-// bf16 inference mode (BAMD_MODE_BF16): encode / decode / forward_loss of AE(F, Z) on v_mfma_f32_16x16x32_bf16.
+// bf16 inference mode (BAMD_MODE_BF16): encode / decode / forward_loss of AE(F, Z) on v_mfma_f32_16x16x32_bf16 -- and its
+// binary16 sibling (BAMD_MODE_F16) on v_mfma_f32_16x16x32_f16: the same kernel with another element type, 11 significant bits.
 //
 // A THROUGHPUT mode, not the parity mode: weights and layer inputs are rounded to bfloat16 (8 significant
 // bits), accumulation is fp32; outputs follow the fp64 reference to ~3e-3 relative (measured, tests), against
@@ -24,7 +25,15 @@
 namespace bamd {
 namespace {
 
+// The 16-bit element type is a template parameter: V = bf8 (bfloat16, BAMD_MODE_BF16) or h8 (IEEE binary16, BAMD_MODE_F16: the
+// contract is in include/baler_amd.h, the measurements in DESIGN.md section 13).  Geometry, LDS staging, loaders and the layer
+// loops are the same text for both; the MFMA builtin, the rounding of a packed value and the activation epilogue (mfma16,
+// pack8, act_pack below) differ.
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+template <class V> struct Elem;
+template <> struct Elem<bf8> { using T = __bf16; };
+template <> struct Elem<h8> { using T = _Float16; };
 using v4 = float __attribute__((ext_vector_type(4)));
 #ifndef BAMD_BF16_KMB
 #define BAMD_BF16_KMB 4
@@ -63,7 +72,8 @@ template <int F, int Z> struct BNet {
     static constexpr size_t lds_bytes(int h) { return (size_t)half_frags(h) * 1024 + (size_t)half_bias(h) * 16 + 4 * 32 * sizeof(double); }
 };
 
-__device__ __forceinline__ v4 mfma_bf16(bf8 a, bf8 b, v4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ v4 mfma16(bf8 a, bf8 b, v4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ v4 mfma16(h8 a, h8 b, v4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
 // LeakyReLU as max(x, 0.01 x) with FOUR v_mul_f32, not two v_pk_mul_f32: a packed fp32 multiply does not overlap the bf16 MFMA of its
 // own wave at all (tools/probe/valu_beside_mfma_probe.hip: + 17 cycles for the first one in an MFMA slot, a plain VALU instruction
@@ -72,17 +82,36 @@ __device__ __forceinline__ void lrelu4(v4 &a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) a[r] = __builtin_elementwise_maximum(a[r], a[r] * 0.01f);
 }
-__device__ __forceinline__ bf8 pack8(const v4 &lo, const v4 &hi) {
-    bf8 o;
+template <class V> __device__ __forceinline__ V pack8(const v4 &lo, const v4 &hi) {      // round to nearest even, no clamp
+    using T = typename Elem<V>::T;
+    V o;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { o[r] = (__bf16)lo[r]; o[4 + r] = (__bf16)hi[r]; }
+    for (int r = 0; r < 4; ++r) { o[r] = (T)lo[r]; o[4 + r] = (T)hi[r]; }
     return o;
+}
+// The epilogue of a tile pair: (activation and) rounding of 8 accumulators to one k-block operand.  has1 = false: `hi` is zero padding.
+//   bfloat16: LeakyReLU in fp32 (lrelu4), then round -- 2.5 VALU instructions per value.
+//   binary16: round FIRST, then max(h, h * slope) on packed binary16 (v_cvt_pk_f16_f32, v_pk_mul_f16, v_pk_maximum3_f16: 1.5 per
+//   value); the slope is the binary16 nearest to 0.01.  BAMD_F16_FP32_LRELU=1 builds the bfloat16 order for binary16 (A/B timing
+//   only: tools/bench_f16_infer.py; its results differ in the last binary16 bit).
+#ifndef BAMD_F16_FP32_LRELU
+#define BAMD_F16_FP32_LRELU 0
+#endif
+template <class V, bool ACT> __device__ __forceinline__ V act_pack(v4 &lo, v4 &hi, bool has1) {
+    if constexpr (std::is_same<V, h8>::value && !BAMD_F16_FP32_LRELU) {
+        V o = pack8<V>(lo, hi);
+        if (ACT) o = __builtin_elementwise_maximum(o, o * (_Float16)kSlope);
+        return o;
+    } else {
+        if (ACT) { lrelu4(lo); if (has1) lrelu4(hi); }
+        return pack8<V>(lo, hi);
+    }
 }
 
 // One Linear (+ LeakyReLU) layer for kMB batch tiles.  w: this layer's fragments in LDS ([q][t], 64 lanes x 16 B
 // each, already offset by the lane); bias: [t][g] float4.  Output tiles are produced in pairs = k blocks of the next layer.
-template <int KB, int NT, bool ACT>
-__device__ __forceinline__ void blayer(const bf8 (&in)[KB][kMB], bf8 (&out)[(NT + 1) / 2][kMB], const bf8 *w, const v4 *bias, int g) {
+template <int KB, int NT, bool ACT, class V>
+__device__ __forceinline__ void blayer(const V (&in)[KB][kMB], V (&out)[(NT + 1) / 2][kMB], const V *w, const v4 *bias, int g) {
 #pragma unroll
     for (int p = 0; p < (NT + 1) / 2; ++p) {
         const bool has1 = 2 * p + 1 < NT;
@@ -93,10 +122,10 @@ __device__ __forceinline__ void blayer(const bf8 (&in)[KB][kMB], bf8 (&out)[(NT 
         for (int mb = 0; mb < kMB; ++mb) { acc0[mb] = b0; acc1[mb] = b1; }
         // fragment reads one step ahead of their MFMAs (hipcc placed every ds_read_b128 right in front of its use: a full LDS
         // round trip before each group of four MFMAs, SQ_WAIT_ANY 45-51 %); sched_barrier pins the order
-        bf8 a0 = w[(2 * p) * 64], a1 = has1 ? w[(2 * p + 1) * 64] : a0;
+        V a0 = w[(2 * p) * 64], a1 = has1 ? w[(2 * p + 1) * 64] : a0;
 #pragma unroll
         for (int q = 0; q < KB; ++q) {
-            bf8 n0 = a0, n1 = a1;
+            V n0 = a0, n1 = a1;
             if (q + 1 < KB) {
                 n0 = w[((q + 1) * NT + 2 * p) * 64];
                 n1 = has1 ? w[((q + 1) * NT + 2 * p + 1) * 64] : n0;
@@ -104,27 +133,24 @@ __device__ __forceinline__ void blayer(const bf8 (&in)[KB][kMB], bf8 (&out)[(NT 
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mb = 0; mb < kMB; ++mb) {
-                acc0[mb] = mfma_bf16(a0, in[q][mb], acc0[mb]);
-                if (has1) acc1[mb] = mfma_bf16(a1, in[q][mb], acc1[mb]);
+                acc0[mb] = mfma16(a0, in[q][mb], acc0[mb]);
+                if (has1) acc1[mb] = mfma16(a1, in[q][mb], acc1[mb]);
             }
             __builtin_amdgcn_sched_barrier(0);
             a0 = n0;
             a1 = n1;
         }
 #pragma unroll
-        for (int mb = 0; mb < kMB; ++mb) {
-            if (ACT) { lrelu4(acc0[mb]); if (has1) lrelu4(acc1[mb]); }
-            out[p][mb] = pack8(acc0[mb], acc1[mb]);      // without a second tile acc1 = 0: zero k slots
-        }
+        for (int mb = 0; mb < kMB; ++mb) out[p][mb] = act_pack<V, ACT>(acc0[mb], acc1[mb], has1);      // without a second tile acc1 = 0: zero k slots
     }
 }
 // Two activated layers back to back with the roles swapped: ALL output tiles of the second layer are accumulators
 // (NT1 x kMB tiles) and every k block of its input is consumed as soon as the first layer has produced it.  For
 // en1 -> en2 this replaces the 200-feature activation (112 registers) + a second set of accumulators by 7 x 4
 // accumulator tiles: the encoder fits 256 registers without scratch.
-template <int KB, int NT, int NT1>
-__device__ __forceinline__ void blayer_pair(const bf8 (&in)[KB][kMB], bf8 (&out)[(NT1 + 1) / 2][kMB], const bf8 *w, const v4 *bias,
-                                            const bf8 *w1, const v4 *bias1, int g) {
+template <int KB, int NT, int NT1, class V>
+__device__ __forceinline__ void blayer_pair(const V (&in)[KB][kMB], V (&out)[(NT1 + 1) / 2][kMB], const V *w, const v4 *bias,
+                                            const V *w1, const v4 *bias1, int g) {
     v4 acc[NT1][kMB];
 #pragma unroll
     for (int t = 0; t < NT1; ++t) {
@@ -142,10 +168,10 @@ __device__ __forceinline__ void blayer_pair(const bf8 (&in)[KB][kMB], bf8 (&out)
         for (int mb = 0; mb < kMB; ++mb) { acc0[mb] = b0; acc1[mb] = b1; }
         // fragment reads one step ahead of their MFMAs (hipcc placed every ds_read_b128 right in front of its use: a full LDS
         // round trip before each group of four MFMAs, SQ_WAIT_ANY 45-51 %); sched_barrier pins the order
-        bf8 a0 = w[(2 * p) * 64], a1 = has1 ? w[(2 * p + 1) * 64] : a0;
+        V a0 = w[(2 * p) * 64], a1 = has1 ? w[(2 * p + 1) * 64] : a0;
 #pragma unroll
         for (int q = 0; q < KB; ++q) {
-            bf8 n0 = a0, n1 = a1;
+            V n0 = a0, n1 = a1;
             if (q + 1 < KB) {
                 n0 = w[((q + 1) * NT + 2 * p) * 64];
                 n1 = has1 ? w[((q + 1) * NT + 2 * p + 1) * 64] : n0;
@@ -153,29 +179,25 @@ __device__ __forceinline__ void blayer_pair(const bf8 (&in)[KB][kMB], bf8 (&out)
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mb = 0; mb < kMB; ++mb) {
-                acc0[mb] = mfma_bf16(a0, in[q][mb], acc0[mb]);
-                if (has1) acc1[mb] = mfma_bf16(a1, in[q][mb], acc1[mb]);
+                acc0[mb] = mfma16(a0, in[q][mb], acc0[mb]);
+                if (has1) acc1[mb] = mfma16(a1, in[q][mb], acc1[mb]);
             }
             __builtin_amdgcn_sched_barrier(0);
             a0 = n0;
             a1 = n1;
         }
-        bf8 blk[kMB];
+        V blk[kMB];
 #pragma unroll
-        for (int mb = 0; mb < kMB; ++mb) {
-            lrelu4(acc0[mb]);
-            if (has1) lrelu4(acc1[mb]);
-            blk[mb] = pack8(acc0[mb], acc1[mb]);
-        }
+        for (int mb = 0; mb < kMB; ++mb) blk[mb] = act_pack<V, true>(acc0[mb], acc1[mb], has1);
         {
-            bf8 a = w1[(p * NT1) * 64];
+            V a = w1[(p * NT1) * 64];
 #pragma unroll
             for (int t = 0; t < NT1; ++t) {
-                bf8 nx = a;
+                V nx = a;
                 if (t + 1 < NT1) nx = w1[(p * NT1 + t + 1) * 64];
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int mb = 0; mb < kMB; ++mb) acc[t][mb] = mfma_bf16(a, blk[mb], acc[t][mb]);
+                for (int mb = 0; mb < kMB; ++mb) acc[t][mb] = mfma16(a, blk[mb], acc[t][mb]);
                 __builtin_amdgcn_sched_barrier(0);
                 a = nx;
             }
@@ -185,12 +207,11 @@ __device__ __forceinline__ void blayer_pair(const bf8 (&in)[KB][kMB], bf8 (&out)
     for (int p = 0; p < (NT1 + 1) / 2; ++p)
 #pragma unroll
         for (int mb = 0; mb < kMB; ++mb) {
-            lrelu4(acc[2 * p][mb]);
             if (2 * p + 1 < NT1) {
-                lrelu4(acc[2 * p + 1][mb]);
-                out[p][mb] = pack8(acc[2 * p][mb], acc[2 * p + 1][mb]);
+                out[p][mb] = act_pack<V, true>(acc[2 * p][mb], acc[2 * p + 1][mb], true);
             } else {
-                out[p][mb] = pack8(acc[2 * p][mb], (v4){0.f, 0.f, 0.f, 0.f});
+                v4 zero = {0.f, 0.f, 0.f, 0.f};
+                out[p][mb] = act_pack<V, true>(acc[2 * p][mb], zero, false);
             }
         }
 }
@@ -198,9 +219,9 @@ __device__ __forceinline__ void blayer_pair(const bf8 (&in)[KB][kMB], bf8 (&out)
 // Layer l (+ LeakyReLU) fused with the LAST layer of the half: every k block of the last layer's input is consumed
 // as soon as its tile pair is finished, so the widest activation (200 features x 64 rows = 112 registers) is never
 // materialised (decode kept 99 registers in scratch without this).
-template <int KB, int NT, int NT2>
-__device__ __forceinline__ void blayer_then_last(const bf8 (&in)[KB][kMB], v4 (&y)[NT2][kMB], const bf8 *w, const v4 *bias,
-                                                 const bf8 *w2, const v4 *bias2, int g) {
+template <int KB, int NT, int NT2, class V>
+__device__ __forceinline__ void blayer_then_last(const V (&in)[KB][kMB], v4 (&y)[NT2][kMB], const V *w, const v4 *bias,
+                                                 const V *w2, const v4 *bias2, int g) {
 #pragma unroll
     for (int t = 0; t < NT2; ++t) {
         const v4 b = bias2[t * 4 + g];
@@ -217,10 +238,10 @@ __device__ __forceinline__ void blayer_then_last(const bf8 (&in)[KB][kMB], v4 (&
         for (int mb = 0; mb < kMB; ++mb) { acc0[mb] = b0; acc1[mb] = b1; }
         // fragment reads one step ahead of their MFMAs (hipcc placed every ds_read_b128 right in front of its use: a full LDS
         // round trip before each group of four MFMAs, SQ_WAIT_ANY 45-51 %); sched_barrier pins the order
-        bf8 a0 = w[(2 * p) * 64], a1 = has1 ? w[(2 * p + 1) * 64] : a0;
+        V a0 = w[(2 * p) * 64], a1 = has1 ? w[(2 * p + 1) * 64] : a0;
 #pragma unroll
         for (int q = 0; q < KB; ++q) {
-            bf8 n0 = a0, n1 = a1;
+            V n0 = a0, n1 = a1;
             if (q + 1 < KB) {
                 n0 = w[((q + 1) * NT + 2 * p) * 64];
                 n1 = has1 ? w[((q + 1) * NT + 2 * p + 1) * 64] : n0;
@@ -228,29 +249,25 @@ __device__ __forceinline__ void blayer_then_last(const bf8 (&in)[KB][kMB], v4 (&
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mb = 0; mb < kMB; ++mb) {
-                acc0[mb] = mfma_bf16(a0, in[q][mb], acc0[mb]);
-                if (has1) acc1[mb] = mfma_bf16(a1, in[q][mb], acc1[mb]);
+                acc0[mb] = mfma16(a0, in[q][mb], acc0[mb]);
+                if (has1) acc1[mb] = mfma16(a1, in[q][mb], acc1[mb]);
             }
             __builtin_amdgcn_sched_barrier(0);
             a0 = n0;
             a1 = n1;
         }
-        bf8 blk[kMB];
+        V blk[kMB];
 #pragma unroll
-        for (int mb = 0; mb < kMB; ++mb) {
-            lrelu4(acc0[mb]);
-            if (has1) lrelu4(acc1[mb]);
-            blk[mb] = pack8(acc0[mb], acc1[mb]);
-        }
+        for (int mb = 0; mb < kMB; ++mb) blk[mb] = act_pack<V, true>(acc0[mb], acc1[mb], has1);
         {
-            bf8 a = w2[(p * NT2) * 64];
+            V a = w2[(p * NT2) * 64];
 #pragma unroll
             for (int t = 0; t < NT2; ++t) {
-                bf8 nx = a;
+                V nx = a;
                 if (t + 1 < NT2) nx = w2[(p * NT2 + t + 1) * 64];
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int mb = 0; mb < kMB; ++mb) y[t][mb] = mfma_bf16(a, blk[mb], y[t][mb]);
+                for (int mb = 0; mb < kMB; ++mb) y[t][mb] = mfma16(a, blk[mb], y[t][mb]);
                 __builtin_amdgcn_sched_barrier(0);
                 a = nx;
             }
@@ -298,8 +315,8 @@ __device__ __forceinline__ void load_block_issue(RawBlock<D, IN> &raw, const voi
         }
     }
 }
-template <int D, int IN>
-__device__ __forceinline__ bf8 load_block_finish(const RawBlock<D, IN> &raw, int g, const double *feats_lds) {
+template <class V, int D, int IN>
+__device__ __forceinline__ V load_block_finish(const RawBlock<D, IN> &raw, int g, const double *feats_lds) {
     float v[8];
     const int f0 = 8 * g < D ? 8 * g : 0;
 #pragma unroll
@@ -310,15 +327,16 @@ __device__ __forceinline__ bf8 load_block_finish(const RawBlock<D, IN> &raw, int
         if (feats_lds) d = (d - feats_lds[f]) / feats_lds[32 + f];
         v[e] = (D % 8 == 0 || 8 * g + e < D) ? (float)d : 0.f;
     }
-    bf8 o;
+    V o;      // round to nearest even; binary16: a value beyond its range becomes +-inf (a binary16 code passes through exactly)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
+    for (int e = 0; e < 8; ++e) o[e] = (typename Elem<V>::T)v[e];
     return o;
 }
 
 // DEC = false: z = encode(x).  DEC = true: out = decode(z) (+ un-normalise / int truncation), and with xref the
 // squared-error partial of out against (normalised) xref rows (forward_loss).
-template <int F, int Z, bool DEC, int IN>
+// (The kernel keeps the name of its first element type; V = h8 is the BAMD_MODE_F16 sibling.)
+template <class V, int F, int Z, bool DEC, int IN>
 __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__restrict__ wfrags, const v4 *__restrict__ bias_g,
                                                                  const void *__restrict__ xin, int64_t n,
                                                                  const double *__restrict__ feats, void *__restrict__ out, int out_f64,
@@ -364,15 +382,15 @@ __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__
     if (pass0 < npass) prefetch(pass0);
     for (int64_t pass = pass0; pass < npass; pass += pstride) {
         asm volatile("" : "+v"(lane_off));              // keep the LDS fragment reads inside the loop (LICM would spill the model)
-        const bf8 *w = (const bf8 *)wl + lane_off;
+        const V *w = (const V *)wl + lane_off;
         int64_t row[kMB];
         bool valid[kMB];
 #pragma unroll
         for (int mb = 0; mb < kMB; ++mb) { row[mb] = pass * kRowsPerPass + 16 * mb + j; valid[mb] = row[mb] < n; }
         if (!DEC) {
-            bf8 a0[1][kMB], a2[N::kb(2)][kMB];
+            V a0[1][kMB], a2[N::kb(2)][kMB];
 #pragma unroll
-            for (int mb = 0; mb < kMB; ++mb) a0[0][mb] = load_block_finish<DIN, IN>(raw[mb], g, feats ? fl : nullptr);
+            for (int mb = 0; mb < kMB; ++mb) a0[0][mb] = load_block_finish<V, DIN, IN>(raw[mb], g, feats ? fl : nullptr);
             if (!IN64) prefetch(pass + pstride);          // float64 rows (16 registers per batch tile): after the widest layer pair
             blayer_pair<N::kb(0), N::nt(0), N::nt(1)>(a0, a2, w + N::f_off(0) * 64, bias + N::b_off(0), w + N::f_off(1) * 64,
                                                       bias + N::b_off(1), g);
@@ -404,9 +422,9 @@ __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__
                 }
             }
         } else {
-            bf8 a4[1][kMB], a5[N::kb(5)][kMB], a6[N::kb(6)][kMB];
+            V a4[1][kMB], a5[N::kb(5)][kMB], a6[N::kb(6)][kMB];
 #pragma unroll
-            for (int mb = 0; mb < kMB; ++mb) a4[0][mb] = load_block_finish<DIN, IN>(raw[mb], g, nullptr);
+            for (int mb = 0; mb < kMB; ++mb) a4[0][mb] = load_block_finish<V, DIN, IN>(raw[mb], g, nullptr);
             if (!IN64) prefetch(pass + pstride);
             blayer<N::kb(4), N::nt(4), true>(a4, a5, w + N::f_off(4) * 64, bias + N::b_off(4), g);
             blayer<N::kb(5), N::nt(5), true>(a5, a6, w + N::f_off(5) * 64, bias + N::b_off(5), g);
@@ -470,11 +488,13 @@ __global__ void __launch_bounds__(64 * kWaves) bf16_infer_kernel(const uint4 *__
     }
 }
 
-// params (fp32, state-dict order) -> bf16 fragments / fp32 bias fragments through precomputed index maps
-__global__ void __launch_bounds__(256) pack_bf16_k(const float *__restrict__ params, const int *__restrict__ src, int count,
-                                                   __bf16 *__restrict__ dst) {
+// params (fp32, state-dict order) -> 16-bit fragments (T: __bf16 or _Float16, round to nearest even) / fp32 bias fragments through
+// precomputed index maps
+template <class T>
+__global__ void __launch_bounds__(256) pack16_k(const float *__restrict__ params, const int *__restrict__ src, int count,
+                                                T *__restrict__ dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) dst[i] = (__bf16)(src[i] >= 0 ? params[src[i]] : 0.f);
+    if (i < count) dst[i] = (T)(src[i] >= 0 ? params[src[i]] : 0.f);
 }
 __global__ void __launch_bounds__(256) pack_bias_k(const float *__restrict__ params, const int *__restrict__ src, int count,
                                                    float *__restrict__ dst) {
@@ -497,10 +517,11 @@ struct Bf16Ops {
                int out_f64, const uint8_t *imask, const void *xref, int xref_f64, const double *xref_feats, double *loss_part,
                hipStream_t s);
     int z_dim, n_features;
+    bool half;                   // the fragments are binary16 (BAMD_MODE_F16), not bfloat16
 };
 Bf16State *bstate(bamd_handle *h) { return (Bf16State *)h->bf16_state; }
 
-template <int F, int Z> struct BImpl {
+template <class V, int F, int Z> struct BImpl {
     using N = BNet<F, Z>;
     static bool matches(const bamd_handle *h) {
         if (h->L != 8) return false;
@@ -542,17 +563,17 @@ template <int F, int Z> struct BImpl {
             BAMD_HIP(hipMemcpy(st->wsrc[hf].p, wsrc.data(), wsrc.size() * sizeof(int), hipMemcpyHostToDevice));
             BAMD_HIP(hipMemcpy(st->bsrc[hf].p, bsrc.data(), bsrc.size() * sizeof(int), hipMemcpyHostToDevice));
         }
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, false, BAMD_F32>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, false, BAMD_F32>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(0)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, false, BAMD_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, false, BAMD_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(0)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, BAMD_F32>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, true, BAMD_F32>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(1)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, BAMD_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, true, BAMD_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(1)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, BAMD_F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, true, BAMD_F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(1)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<F, Z, true, BAMD_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, true, BAMD_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)N::lds_bytes(1)));
         return BAMD_OK;
     }
@@ -565,7 +586,7 @@ template <int F, int Z> struct BImpl {
         auto go = [&](auto decv, auto inv) {      // in_f64 / out_f64 are bamd_dtype codes: 16-bit for the latent side of a decode / an encode
             constexpr bool D_ = decltype(decv)::value;
             constexpr int I_ = decltype(inv)::value;
-            hipLaunchKernelGGL((bf16_infer_kernel<F, Z, D_, I_>), dim3(grid), dim3(64 * kWaves), N::lds_bytes(D_ ? 1 : 0), s,
+            hipLaunchKernelGGL((bf16_infer_kernel<V, F, Z, D_, I_>), dim3(grid), dim3(64 * kWaves), N::lds_bytes(D_ ? 1 : 0), s,
                                (const uint4 *)st->w[D_ ? 1 : 0].p, (const v4 *)st->b[D_ ? 1 : 0].p, xin, n, feats, out, out_f64, imask, xref,
                                xref_f64, xref_feats, loss_part);
         };
@@ -581,33 +602,33 @@ template <int F, int Z> struct BImpl {
         return grid;
     }
     static const Bf16Ops *ops() {
-        static const Bf16Ops o = {setup, run, Z, F};
+        static const Bf16Ops o = {setup, run, Z, F, std::is_same<V, h8>::value};
         return &o;
     }
 };
 
-const Bf16Ops *find_bf16(const bamd_handle *h) {
-    if (BImpl<24, 15>::matches(h)) return BImpl<24, 15>::ops();
-    if (BImpl<24, 12>::matches(h)) return BImpl<24, 12>::ops();
-    if (BImpl<24, 8>::matches(h)) return BImpl<24, 8>::ops();
-    if (BImpl<24, 6>::matches(h)) return BImpl<24, 6>::ops();
+template <class V> const Bf16Ops *find16(const bamd_handle *h) {
+    if (BImpl<V, 24, 15>::matches(h)) return BImpl<V, 24, 15>::ops();
+    if (BImpl<V, 24, 12>::matches(h)) return BImpl<V, 24, 12>::ops();
+    if (BImpl<V, 24, 8>::matches(h)) return BImpl<V, 24, 8>::ops();
+    if (BImpl<V, 24, 6>::matches(h)) return BImpl<V, 24, 6>::ops();
     // the other latent sizes of the compression-ratio knob (see fused.hip find_ops)
-    if (BImpl<24, 10>::matches(h)) return BImpl<24, 10>::ops();
-    if (BImpl<24, 5>::matches(h)) return BImpl<24, 5>::ops();
-    if (BImpl<24, 4>::matches(h)) return BImpl<24, 4>::ops();
-    if (BImpl<24, 3>::matches(h)) return BImpl<24, 3>::ops();
-    if (BImpl<24, 2>::matches(h)) return BImpl<24, 2>::ops();
+    if (BImpl<V, 24, 10>::matches(h)) return BImpl<V, 24, 10>::ops();
+    if (BImpl<V, 24, 5>::matches(h)) return BImpl<V, 24, 5>::ops();
+    if (BImpl<V, 24, 4>::matches(h)) return BImpl<V, 24, 4>::ops();
+    if (BImpl<V, 24, 3>::matches(h)) return BImpl<V, 24, 3>::ops();
+    if (BImpl<V, 24, 2>::matches(h)) return BImpl<V, 24, 2>::ops();
     return nullptr;
 }
 
 }  // namespace
 
-bool bf16_has_kernels(const bamd_handle *h) { return h->leaky() && find_bf16(h) != nullptr; }
+bool bf16_has_kernels(const bamd_handle *h) { return h->leaky() && find16<bf8>(h) != nullptr; }      // (the same shapes for both types)
 
 int bf16_setup(bamd_handle *h) {
-    const Bf16Ops *ops = h->leaky() ? find_bf16(h) : nullptr;
+    const Bf16Ops *ops = !h->leaky() ? nullptr : h->mode == BAMD_MODE_F16 ? find16<h8>(h) : find16<bf8>(h);
     if (!ops) {
-        set_error("BAMD_MODE_BF16 is instantiated for the 24-column AE (latent 15/12/8/6) and the wide models (2500-25, 512-6) only; use BAMD_MODE_F32");
+        set_error("BAMD_MODE_BF16 / BAMD_MODE_F16 are instantiated for the 24-column AE (latent 15/12/8/6) and the wide models (2500-25, 512-6) only; use BAMD_MODE_F32");
         return BAMD_ERR_UNSUPPORTED;
     }
     Bf16State *st = new Bf16State();
@@ -628,8 +649,12 @@ void bf16_teardown(bamd_handle *h) {
 int bf16_pack(bamd_handle *h, hipStream_t s) {
     Bf16State *st = bstate(h);
     for (int hf = 0; hf < 2; ++hf) {
-        hipLaunchKernelGGL(pack_bf16_k, dim3((st->wcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
-                           (const int *)st->wsrc[hf].p, st->wcount[hf], (__bf16 *)st->w[hf].p);
+        if (st->ops->half)
+            hipLaunchKernelGGL(pack16_k<_Float16>, dim3((st->wcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
+                               (const int *)st->wsrc[hf].p, st->wcount[hf], (_Float16 *)st->w[hf].p);
+        else
+            hipLaunchKernelGGL(pack16_k<__bf16>, dim3((st->wcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
+                               (const int *)st->wsrc[hf].p, st->wcount[hf], (__bf16 *)st->w[hf].p);
         hipLaunchKernelGGL(pack_bias_k, dim3((st->bcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
                            (const int *)st->bsrc[hf].p, st->bcount[hf], (float *)st->b[hf].p);
     }

@@ -1,11 +1,12 @@
-// bf16 inference mode (bf16.hip): encode / decode / forward_loss on v_mfma_f32_16x16x32_bf16 with LDS-resident weights.
+// bf16 / f16 inference modes (bf16.hip): encode / decode / forward_loss on v_mfma_f32_16x16x32_bf16 / _f16 with LDS-resident weights.
+// One state per handle (h->bf16_state); its element type follows h->mode at bf16_setup (BAMD_MODE_F16: IEEE binary16).
 #pragma once
 #include "bamd_internal.hpp"
 
 namespace bamd {
-bool bf16_has_kernels(const bamd_handle *h);     // this shape has a bf16 inference instantiation in bf16.hip
+bool bf16_has_kernels(const bamd_handle *h);     // this shape has a bf16 (and an f16) inference instantiation in bf16.hip
 int bf16_setup(bamd_handle *h);                  // BAMD_ERR_UNSUPPORTED for shapes without an instantiation
-int bf16_pack(bamd_handle *h, hipStream_t s);    // h->params (fp32) -> bf16 fragments + fp32 bias fragments
+int bf16_pack(bamd_handle *h, hipStream_t s);    // h->params (fp32) -> bf16 / f16 fragments + fp32 bias fragments
 void bf16_teardown(bamd_handle *h);
 int bf16_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype,
                 hipStream_t s);

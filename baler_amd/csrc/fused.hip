@@ -4793,7 +4793,7 @@ static bool mid_width_hybrid() {
     return wide_class_on() && !(e && e[0] == '0');
 }
 static const FusedOps *find_small_ops(const bamd_handle *h) {
-    if (h->mode != BAMD_MODE_F32) return nullptr;
+    if (!h->f32_compute()) return nullptr;
     if (ImplInferClass<79, 31, true>::matches(h)) return ImplInferClass<79, 31, true>::ops();
     if (ImplInferClass<95, 31, true>::matches(h)) return ImplInferClass<95, 31, true>::ops();
     if (ImplInferClass<111, 31, true>::matches(h)) return ImplInferClass<111, 31, true>::ops();
@@ -4810,7 +4810,7 @@ static const FusedOps *find_ops(const bamd_handle *h) {
         BAMD_AE24_ALL
         return nullptr;
     }
-    if (h->mode != BAMD_MODE_F32) return nullptr;
+    if (!h->f32_compute()) return nullptr;
     BAMD_AE24_ALL
     // any other narrow table: the class instantiations (run-time widths; Impl<F, Z, true>): up to 63 columns with a latent of up to
     // 31 on every kernel, 64..79 columns on the one-tile inference and the small-batch kernels (ImplInferClass).  80 columns and

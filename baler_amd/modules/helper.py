@@ -360,6 +360,23 @@ def _check_float16_range(h, flat, feats, out, world):
                          "(float32's range at 8 bits of precision) or leave latent_dtype unset.")
 
 
+def _check_fp16_mode_range(h, rows_in, rows_out, world, what):
+    """The fp16 compute mode (BAMD_MODE_F16: binary16 layer inputs, include/baler_amd.h): a value beyond +-65504 inside the chain turns
+    every output of ITS row non-finite.  Count, on the device, the rows whose input is entirely finite but whose output is not (rows
+    that came in with NaN / inf pass through as in every mode) and refuse to go on if there are any.  Every rank takes part and
+    every rank raises.  Handles that compute in another mode are not checked."""
+    if h.compute_mode != native.MODE_F16:
+        return
+    bad = (torch.isfinite(rows_in).all(dim=1) & ~torch.isfinite(rows_out).all(dim=1)).sum().to(torch.float64).reshape(1)
+    if world > 1:
+        bdist.allreduce_sum(bad)
+    count = int(bad.item())
+    if count:
+        raise ValueError(f"BALER_AMD_MODE=fp16: {count} rows with finite input left the float16 range (|value| > 65504) inside the "
+                         f"model and {what} to non-finite values; nothing is written.  Use the bf16 mode (BALER_AMD_MODE=bf16: "
+                         "float32's range at 8 bits of precision) or the fp32 mode (BALER_AMD_MODE=fp32) for this model and data.")
+
+
 def compress(model_path, config):
     """reference helper.py:473-616.  Returns (compressed ndarray, batches, deltas, indices); the last three are
     empty lists unless ``config.save_error_bounded_deltas`` (then: batch numbers, one float16 array per batch and
@@ -424,6 +441,7 @@ def compress(model_path, config):
         ready.append((e, ev))
     if latent_dtype == "float16":       # before the gather and the download: an overflowing run fails without moving the codes
         _check_float16_range(h, flat, feats, out, world)
+    _check_fp16_mode_range(h, flat, out, world, "encode")
     # bfloat16 codes travel as a float16-typed view: a 2-byte carrier every collective and numpy know; no copy interprets it
     compressed = _gather_rows(out.view(torch.float16) if latent_dtype == "bfloat16" else out, n_total, world, ready)
     if latent_dtype == "bfloat16":
@@ -565,6 +583,7 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
         ev = torch.cuda.Event()
         ev.record()
         ready.append((e, ev))
+    _check_fp16_mode_range(h, z, out, world, "decode")
     if want_deltas:
         ready = None
         rows, cols, vals = load_deltas(input_path_deltas, input_batch_index, config.batch_size)

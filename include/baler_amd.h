@@ -79,8 +79,26 @@ typedef enum bamd_dtype { BAMD_F32 = 0, BAMD_F64 = 1, BAMD_F16 = 2, BAMD_BF16 = 
  * ~1e-3 rel-L2, which is the rounding of those wide operands; BALER_AMD_BF16_WIDE_TRAIN=0: the F32 launches); validation of such a handle runs
  * in fp32; any OTHER shape asked for in BAMD_MODE_BF16 is created as a float32 handle (run-time-width fused classes or the layer-wise
  * kernels, whatever serves the shape in BAMD_MODE_F32) with a notice on stderr -- bamd_mode_of() then returns BAMD_MODE_F32.  bamd_activation_means of a BF16 handle runs on the fp32
- * layer-wise kernels. */
-typedef enum bamd_mode { BAMD_MODE_F32 = 0, BAMD_MODE_F64 = 1, BAMD_MODE_BF16 = 2 } bamd_mode;
+ * layer-wise kernels.
+ * F16 = v_mfma_f32_16x16x32_f16 with fp32 accumulation: the second THROUGHPUT mode, for INFERENCE only -- the MFMA rate and operand
+ * layout of BF16 with IEEE binary16's 11 significant bits instead of 8 (measured against the fp64 reference: about one eighth of the
+ * BF16 error).  It serves bamd_encode, bamd_decode and bamd_forward_loss of the 24-column AE at every fused latent size (15, 12, 10,
+ * 8, 6, 5, 4, 3, 2).  Arithmetic: weights are rounded to nearest even from the fp32 master copy to binary16 when they are packed;
+ * layer inputs are binary16 (rows, normalised in float64 first; latent codes on decode; activations); biases and accumulation are
+ * fp32; after every activated layer the fp32 accumulator is rounded to binary16 (nearest even, NO clamp) and LeakyReLU is
+ * max(h, h * s) in binary16, s = the binary16 nearest to 0.01; the two un-activated outputs (latent, reconstruction) stay fp32 and
+ * go through the epilogues of the BF16 mode (un-normalise + int truncation, loss partials, every z_dtype).  On bamd_decode BAMD_F16
+ * codes are binary16 already and enter the chain WITHOUT a rounding (BAMD_BF16 / float codes are rounded to binary16).
+ * Range: data normalised to [0, 1] and the activations of a trained model (largest seen: 6.9) are far inside binary16's range
+ * (65504).  A value that leaves it becomes +-inf, and every output of THAT ROW becomes non-finite (inf or NaN); no other row is
+ * affected (rows are MFMA columns, they never mix).  Callers that cannot rule this out check their outputs, as
+ * baler_amd's compress / decompress do, and fall back to BAMD_MODE_BF16 or BAMD_MODE_F32.
+ * Everything else on an F16 handle is exact fp32: bamd_fwd_bwd, bamd_train_step, bamd_train_epoch(_dp) and bamd_adam_step run the
+ * kernels a BAMD_MODE_F32 handle of the same shape runs, at every batch size, with bit-identical results (params / m / v / grads
+ * are FLOAT); the binary16 fragments are re-rounded lazily after an optimiser step or bamd_load_params; bamd_activation_means runs
+ * on the fp32 layer-wise kernels.  Any shape without F16 kernels (other column counts, the wide models, BAMD_ACT_RELU handles,
+ * PJ_Conv_AE) is created as a float32 handle with one notice on stderr, and bamd_mode_of() returns BAMD_MODE_F32. */
+typedef enum bamd_mode { BAMD_MODE_F32 = 0, BAMD_MODE_F64 = 1, BAMD_MODE_BF16 = 2, BAMD_MODE_F16 = 3 } bamd_mode;
 
 /* Adam hyper-parameters of one step (torch.optim.Adam defaults are beta1=.9 beta2=.999 eps=1e-8). */
 typedef struct bamd_adam {
@@ -114,7 +132,7 @@ typedef enum bamd_act {
  * de1 and de2.  ReLU follows torch: relu(nan) = nan, relu(-inf) = 0, and the backward pass lets the gradient through where the
  * layer's output is > 0 (threshold_backward; an exact-zero pre-activation gets a zero gradient).  A BAMD_ACT_RELU handle runs on the
  * fused FPGA_prototype_model kernels (fpga.hip) for n_features <= 64 and z <= 32 in BAMD_MODE_F32 / BAMD_MODE_F64, and on the
- * layer-wise kernels for every other shape; the LeakyReLU kernel families never serve it.  In BAMD_MODE_BF16 it is created as a
+ * layer-wise kernels for every other shape; the LeakyReLU kernel families never serve it.  In BAMD_MODE_BF16 / BAMD_MODE_F16 it is created as a
  * float32 handle with a notice on stderr.  The activation-means diagnostic returns BAMD_ERR_UNSUPPORTED for it (the reference model
  * has no activation hooks either, training.py:287). */
 int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device, bamd_handle **out);
@@ -132,7 +150,7 @@ int bamd_act_of(const bamd_handle *h);     /* the handle's bamd_act, or BAMD_ERR
  * parameters.  The loss of bamd_forward_loss / bamd_fwd_bwd is utils.mse_sum_loss_l1(validate=True) (utils.py:176-211) of the
  * reference's 2-D path, whose divisor is true_data.shape[1] = the channel count, 1: the PLAIN sum of squared errors, not divided by 784.
  * Arithmetic: v_mfma_f32_16x16x4_f32 (exact fp32) implicit GEMMs, fixed-order weight-gradient sums: bitwise repeatable.
- * z_dim: 1 .. 2450 (else BAMD_ERR_INVALID).  mode: BAMD_MODE_F32; BAMD_MODE_BF16 gives a float32 handle with a notice on stderr
+ * z_dim: 1 .. 2450 (else BAMD_ERR_INVALID).  mode: BAMD_MODE_F32; BAMD_MODE_BF16 / BAMD_MODE_F16 give a float32 handle with a notice on stderr
  * (bamd_mode_of() reports BAMD_MODE_F32); BAMD_MODE_F64 returns BAMD_ERR_UNSUPPORTED.  Served on such a handle: bamd_encode,
  * bamd_decode (with the un-normalise / int-mask epilogue), bamd_forward_loss, bamd_fwd_bwd, bamd_adam_step, bamd_train_step,
  * bamd_train_epoch, bamd_train_epoch_dp (and the communicator calls), bamd_load_params, bamd_param_count, bamd_path_of
@@ -167,12 +185,13 @@ typedef enum bamd_path {
     BAMD_PATH_GENERIC = 0,   /* generic.hip: LDS-tiled MFMA GEMM per layer */
     BAMD_PATH_FUSED = 1,     /* fused.hip: register chain (24-column AE) or streamed wide layers + chain */
     BAMD_PATH_BF16 = 2,      /* bf16.hip / bf16_train.hip (24-column AE, BAMD_MODE_BF16); its small batches use the fused fp32 step */
-    BAMD_PATH_FUSED_INFER = 3 /* 64..127 columns with BALER_AMD_MID_HYBRID=0 or BALER_AMD_WIDE_CLASS=0: fused.hip for encode / decode / forward + loss and
+    BAMD_PATH_FUSED_INFER = 3, /* 64..127 columns with BALER_AMD_MID_HYBRID=0 or BALER_AMD_WIDE_CLASS=0: fused.hip for encode / decode / forward + loss and
                               * the small-batch training kernels (larger batches chunk after chunk on the same kernels) */
+    BAMD_PATH_F16 = 4        /* bf16.hip's binary16 instantiations for inference (24-column AE, BAMD_MODE_F16); training on the fused fp32 kernels */
 } bamd_path;
 int bamd_path_of(const bamd_handle *h);   /* a bamd_path, or BAMD_ERR_INVALID for a null handle */
 int64_t bamd_param_count(const bamd_handle *h);
-int bamd_mode_of(const bamd_handle *h);    /* the mode the handle COMPUTES in (BAMD_MODE_BF16 asked of a shape without bf16 kernels: BAMD_MODE_F32) */
+int bamd_mode_of(const bamd_handle *h);    /* the mode the handle COMPUTES in (BAMD_MODE_BF16 / BAMD_MODE_F16 asked of a shape without such kernels: BAMD_MODE_F32) */
 
 /* (Re)build the handle's MFMA-fragment-packed weight copy from the caller's flat parameter vector
  * (device pointer; dtype F32 or F64).  Call after loading a checkpoint or changing params outside

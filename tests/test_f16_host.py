@@ -1,0 +1,137 @@
+"""The fp16 inference mode (BAMD_MODE_F16) on the host: the ABI constants, the mode names, and a numpy emulation of the mode's
+arithmetic contract (include/baler_amd.h) that the GPU tests compare the kernels with.
+
+The emulation, ``f16_chain``: weights rounded to binary16 from the float32 master copy; every layer input rounded to binary16 (rows:
+float64 -> float32 -> binary16, as the kernel's loader does); float32 accumulation and float32 biases; after an activated layer the
+accumulator is rounded to binary16 and LeakyReLU is max(h, h * s) IN binary16 with s = binary16(0.01); the two un-activated
+outputs (latent, reconstruction) stay float32.  ``chain16`` is the same text with the rounding as a parameter, so that the same
+emulation with bfloat16 rounding gives the yardstick the feature is measured against."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from baler_amd import hostio, native, synth
+from baler_amd.modules import models
+from oracle import c_oracle as orc
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def round_f16(a):
+    """float32 array -> the float32 values of its binary16 rounding (nearest even; beyond 65504: +-inf)."""
+    with np.errstate(over="ignore"):
+        return np.asarray(a, dtype=np.float32).astype(np.float16).astype(np.float32)
+
+
+def round_bf16(a):
+    return hostio.bf16_widen(hostio.bf16_bits(np.asarray(a, dtype=np.float32))).astype(np.float32)
+
+
+def chain16(dims, flat, x, lo, hi, rnd):
+    """Layers lo .. hi - 1 of the autoencoder `dims` (encode: 0, 4; decode: 4, 8; forward: 0, 8) on rows `x`, in the 16-bit
+    inference arithmetic whose rounding is `rnd`.  Returns float32."""
+    flat32 = np.asarray(flat, dtype=np.float64).astype(np.float32)
+    L = len(dims) - 1
+    slope = rnd(np.float32(0.01))
+    h = np.asarray(x, dtype=np.float64).astype(np.float32)
+    off = 0
+    offs = []
+    for l in range(L):
+        offs.append(off)
+        off += dims[l + 1] * dims[l] + dims[l + 1]
+    with np.errstate(over="ignore", invalid="ignore"):
+        for l in range(lo, hi):
+            K, N = dims[l], dims[l + 1]
+            w = rnd(flat32[offs[l]:offs[l] + N * K].reshape(N, K))
+            b = flat32[offs[l] + N * K:offs[l] + N * K + N]
+            acc = (rnd(h) @ w.T + b).astype(np.float32)
+            if l == L // 2 - 1 or l == L - 1:
+                h = acc                                            # latent / reconstruction: float32
+            else:
+                h16 = rnd(acc)
+                h = np.maximum(h16, rnd(h16 * slope))              # LeakyReLU in the 16-bit type (the product is rounded to it)
+    return h
+
+
+def f16_chain(dims, flat, x, lo, hi):
+    return chain16(dims, flat, x, lo, hi, round_f16)
+
+
+def bf16_chain(dims, flat, x, lo, hi):
+    return chain16(dims, flat, x, lo, hi, round_bf16)
+
+
+def rel_l2(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+def c1_model():
+    """The trained C1 fixture: AE(24, 15), float32 final parameters."""
+    flat = np.load(os.path.join(REPO, "tests", "golden", "g7_c1_model_f32.npz"))["final_params_f32"].astype(np.float64)
+    return orc.ae_dims(24, 15), flat
+
+
+def three_errors(chain, dims, flat, x):
+    """rel-L2 errors (encode, decode of the oracle's codes, forward) of an emulation against the fp64 oracle."""
+    zo = orc.encode(dims, flat, x)
+    return (rel_l2(chain(dims, flat, x, 0, 4), zo), rel_l2(chain(dims, flat, zo, 4, 8), orc.decode(dims, flat, zo)),
+            rel_l2(chain(dims, flat, x, 0, 8), orc.forward(dims, flat, x)))
+
+
+def test_header_declares_the_mode_and_the_path():
+    header = open(os.path.join(REPO, "include", "baler_amd.h")).read()
+    assert re.search(r"\bBAMD_MODE_F16\s*=\s*3\b", header)
+    assert re.search(r"\bBAMD_PATH_F16\s*=\s*4\b", header)
+    assert "BAMD_ABI_VERSION 1" in header
+
+
+def test_mode_names():
+    assert native.MODE_NAMES["fp16"] == 3 and native.MODE_NAMES["f16"] == 3 and native.MODE_F16 == 3
+    assert native.MODE_NAMES["bf16"] == 2 and native.MODE_NAMES["fp32"] == 0 and native.MODE_NAMES["fp64"] == 1
+    assert len(native.SYMBOLS) == 38                                 # a mode, not an entry point
+
+
+def test_set_default_mode_accepts_fp16_and_refuses_unknown_names():
+    before = models._DEFAULT_MODE
+    try:
+        models.set_default_mode("fp16")
+        assert models._DEFAULT_MODE == "fp16"
+        m = models.AE(24, 15)
+        assert m.mode == "fp16" and m.flat.dtype.is_floating_point and m.flat.element_size() == 4      # float32 master parameters
+        with pytest.raises(ValueError):
+            models.set_default_mode("fp8")
+        assert models._DEFAULT_MODE == "fp16"
+    finally:
+        models.set_default_mode(before)
+
+
+def test_rounding_helpers():
+    a = np.array([1.0, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, 65504.0, 65520.0, 1e6, -1e6, 6e-8], dtype=np.float32)
+    got = round_f16(a)
+    assert list(got[:4]) == [1.0, 1.0, 1.0 + 2.0 ** -9, 65504.0]      # ties to even
+    assert np.isposinf(got[4]) and np.isposinf(got[5]) and np.isneginf(got[6])      # no clamp
+    assert got[7] == np.float32(2.0 ** -24)                            # subnormals are produced
+    assert round_f16(np.float32(0.01)) == np.float32(np.float16(0.01))
+
+
+CASES = [pytest.param("c1", 0, id="trained-c1")] + [pytest.param(z, s, id=f"formula-z{z}-seed{s}") for z in (15, 2) for s in (1, 23)]
+
+
+@pytest.mark.parametrize("z,seed", CASES)
+def test_emulated_fp16_error_is_a_quarter_of_bf16_or_less(z, seed):
+    """Three more significand bits give 2^3; the feature's bar is half of that.  (Ratios seen on the CPU: 7.4 - 9.4.)"""
+    if z == "c1":
+        dims, flat = c1_model()
+        x = orc.normalize(synth.cms_rows(4096))
+    else:
+        dims = orc.ae_dims(24, z)
+        flat = orc.formula_params(dims, seed)
+        x = np.random.default_rng(7).random((4096, 24))
+    e16 = three_errors(f16_chain, dims, flat, x)
+    eb = three_errors(bf16_chain, dims, flat, x)
+    for what, a, b in zip(("encode", "decode", "forward"), e16, eb):
+        print(f"{what}: fp16 {a:.3e}  bf16 {b:.3e}  ratio {b / a:.2f}")
+        assert a <= b / 4, what
