@@ -80,6 +80,47 @@ typedef enum bamd_dtype { BAMD_F32 = 0, BAMD_F64 = 1, BAMD_F16 = 2, BAMD_BF16 = 
  * in fp32; any OTHER shape asked for in BAMD_MODE_BF16 is created as a float32 handle (run-time-width fused classes or the layer-wise
  * kernels, whatever serves the shape in BAMD_MODE_F32) with a notice on stderr -- bamd_mode_of() then returns BAMD_MODE_F32.  bamd_activation_means of a BF16 handle runs on the fp32
  * layer-wise kernels.
+ * BF16 arithmetic, of the 24-column AE and of the wide models (tests/bf16_ref.py is this paragraph as NumPy; the kernels are held
+ * to it element by element, tests/test_gpu_bf16_contract.py).  Every rounding to bfloat16 is to nearest even; the order of an
+ * fp32 sum is not part of the contract.
+ *   Inference.  Weights: bfloat16, rounded from the fp32 master copy when they are packed.  Biases: fp32 -- the start value of
+ *   the fp32 accumulator.  Rows: float64 (float32 rows widened; normalised as (x - min) / range in float64 when features are
+ *   given) -> ONE rounding to float32 -> bfloat16.  Per layer a = b + sum_k W[., k] h[k] in fp32; an activated layer hands
+ *   bfloat16(max(a, a * 0.01f)) on: LeakyReLU on the fp32 accumulator with the fp32 slope, then one rounding per layer input.
+ *   The latent and the reconstruction stay fp32.  bamd_forward_loss is bamd_encode then bamd_decode: the fp32 latent is rounded
+ *   to bfloat16 by the decoder's loader (as float / BAMD_F16 codes are; BAMD_BF16 codes enter exactly); its loss is the float64
+ *   sum of (fp32 reconstruction - fp32 row)^2 / n_features.  Un-normalisation: float64(reconstruction) * range + min, two
+ *   float64 roundings, trunc() on the int columns, then the output dtype.
+ *   Training (batches above the small-batch threshold).  Weights AND biases: bfloat16 -- the bias is input column K of the
+ *   packed weights and meets a ones column of the layer's input image, so it is one more bfloat16 x bfloat16 product of the
+ *   fp32 sum (inference keeps it fp32: the two differ by the bias's rounding, 1e-3 to 2.5e-3 rel-L2 of an encode /
+ *   decode).  Every layer input is
+ *   a bfloat16 image, the latent included; the forward pass is otherwise the inference one.  e = fp32 reconstruction - fp32 row
+ *   (not the row's bfloat16 image); loss = float64 sum of e^2 / n_features; dL/drecon = e * (2.0f / n_features) in fp32, rounded
+ *   to bfloat16.  Backward: dX_l = dZ_l W_l with the forward's bfloat16 weights and fp32 sums; dZ_{l-1} = bfloat16(dX_l) where
+ *   the STORED bfloat16 activation is >= 0 and bfloat16(dX_l * 0.01f) where its sign bit is set (the derivative is taken from
+ *   the activation, not the pre-activation; no mask below the latent); [dW_l | db_l] = dZ_l^T [X_l | 1]: bfloat16 x bfloat16
+ *   products, fp32 sums over the batch in a fixed order (bitwise repeatable).  Gradients and loss are stored as FLOAT.
+ *   Wide models, bamd_encode / bamd_decode.  en1 and de4 follow the inference contract above (operands rounded to bfloat16, the
+ *   fp32 bias as start value, LeakyReLU on the fp32 accumulator).  The six narrow layers follow it too in bamd_decode and in
+ *   bamd_encode of FLOAT32 rows whose length is a multiple of 16 bytes and at least 192 columns (2500 and 512 columns; raw rows
+ *   with features are normalised in float64 into a float32 workspace first and then take this path); in every other bamd_encode
+ *   (FLOAT64 rows, 625 columns) the narrow layers run in exact fp32 on the fp32 master weights and their inputs are not
+ *   rounded.  With features, bamd_decode un-normalises the float32 reconstruction with bamd_renormalize's arithmetic.
+ *   bamd_forward_loss runs in fp32.
+ *   Wide models, training (batches above BALER_AMD_WIDE_SMALL_ROWS, default 8192; smaller ones run the F32 launches).  Rows:
+ *   float32 (FLOAT64 and raw rows: float64 -> one rounding to float32).  Forward: en1 and de4 round their input (the row; the
+ *   fp32 activation y7) and their weights to bfloat16, fp32 bias as start value, fp32 sums; the SIX narrow layers -- which
+ *   inference runs on the bf16 MFMA where the line above says so -- run in exact fp32 on the fp32 master weights; every
+ *   activation is stored in fp32 and never rounded.  e = fp32 reconstruction - fp32 row; loss = float64 sum of e^2 /
+ *   n_features; dL/drecon = e * (2.0f / n_features), and THIS is the one bfloat16 gradient: stored as bfloat16 when n_features
+ *   is a multiple of 4 (BALER_AMD_BF16_DZ16=0: fp32) and rounded to bfloat16 by both of its readers either way.  Backward:
+ *   de4's input-gradient product is bfloat16(dL/drecon) x bfloat16(W) with fp32 sums; the masks are y > 0 ? 1 : 0.01f on the
+ *   stored fp32 activations; layers de3 .. en2 and every dZ below de4 are exact fp32.  Weight gradients: [dW | db] of de4 =
+ *   bfloat16(dL/drecon)^T [bfloat16(y7) | 1] and of en1 = bfloat16(dZ)^T [bfloat16(row) | 1], fp32 sums in a fixed order --
+ *   in passes of at least 128 rows; in a smaller pass these two products, like the narrow layers', are exact fp32 on the
+ *   UNROUNDED fp32 dL/drecon, dZ, rows and y7.  The six narrow layers' gradients are exact fp32 from the fp32 dZ and
+ *   activations always.  All biases are fp32 throughout.
  * F16 = v_mfma_f32_16x16x32_f16 with fp32 accumulation: the second THROUGHPUT mode, for INFERENCE only -- the MFMA rate and operand
  * layout of BF16 with IEEE binary16's 11 significant bits instead of 8 (measured against the fp64 reference: about one eighth of the
  * BF16 error).  It serves bamd_encode, bamd_decode and bamd_forward_loss of the 24-column AE at every fused latent size (15, 12, 10,

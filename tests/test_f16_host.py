@@ -60,6 +60,10 @@ def f16_chain(dims, flat, x, lo, hi):
 
 
 def bf16_chain(dims, flat, x, lo, hi):
+    """The YARDSTICK the fp16 feature is measured against: the binary16 contract's text with bfloat16 rounding.  It is NOT the
+    contract of the bf16 kernels -- it rounds before the LeakyReLU and takes the slope as bfloat16(0.01), they apply LeakyReLU to the
+    fp32 accumulator with the fp32 slope and round once; that contract is tests/bf16_ref.py, and the kernels are held to it in
+    tests/test_gpu_bf16_contract.py."""
     return chain16(dims, flat, x, lo, hi, round_bf16)
 
 
