@@ -104,6 +104,31 @@ def test_roles_pair_class_handle(throughput_pair):
     check(dims, flat, x, dev(x), throughput_pair)
 
 
+# one shape per tile count the shared text of the four kernels is instantiated for
+TILE_SHAPES = [
+    (24, 2),     # Impl<24, 2>: partial latent tile, two live slots
+    (24, 12),    # Impl<24, 12>: partial latent tile
+    (40, 10),    # Impl<47, 15, RT>: three input tiles
+    (30, 20),    # Impl<31, 31, RT>: two latent tiles
+    (45, 20),    # Impl<47, 31, RT>
+    (60, 5),     # Impl<63, 15, RT>: four input tiles, bias fragments read from L2
+    (63, 31),    # Impl<63, 31, RT>
+]
+
+
+@pytest.mark.parametrize("n", [65, 130])
+@pytest.mark.parametrize("shape", TILE_SHAPES, ids=lambda s: f"ae{s[0]}_{s[1]}")
+def test_roles_pair_every_tile_count(shape, n, throughput_pair):
+    """Every instantiation family of the pair at n = 65 (a full group and a one-row group) and n = 130, on the throughput pair.  The
+    two 24-column shapes have both layouts; for the classes the knob picks the same kernel twice (see the class case above).  Rows
+    are plain seeded uniform draws, as in the cases above: none of the fourteen puts a float32 pre-activation on the other side of the
+    LeakyReLU kink than its float64 twin (rel 1.5e-7 .. 2.9e-7), so none needs test_gpu_parity.off_the_kink."""
+    dims = orc.ae_dims(*shape)
+    flat = orc.formula_params(dims, 100 * shape[0] + shape[1])
+    x = np.random.default_rng(1000 * shape[0] + n).random((n, shape[0]))
+    check(dims, flat, x, dev(x), throughput_pair)
+
+
 def test_roles_pair_train_step_equals_fwd_bwd_then_adam(throughput_pair):
     """bamd_train_step == bamd_fwd_bwd + bamd_adam_step, bit for bit, on the role-split pair at n = 130."""
     throughput_pair.setenv("BALER_AMD_TRAIN_ROLES", "1")
