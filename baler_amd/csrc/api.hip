@@ -55,15 +55,17 @@ struct DeviceGuard {
 };
 // ---- the kernel families: their precedence is written down HERE, once for inference and once for training, and every entry point
 // below switches on one of the two routes (a new family is added there).  PjConv: pjconv.hip; Bf16: bf16.hip,
-// bf16_train.hip; F16: the binary16 instantiations of bf16.hip (inference only: such a handle TRAINS on Fused, like an F32 handle); Fpga: fpga.hip; Fused: the fp32 register chain and wide-layer kernels of fused.hip; Fused64: the fp64 chain;
+// bf16_train.hip; F16: the binary16 instantiations of bf16.hip (inference only: such a handle TRAINS on Fused, like an F32 handle); F16X3: f16x3.hip
+// (inference only, like F16); Fpga: fpga.hip; Fused: the fp32 register chain and wide-layer kernels of fused.hip; Fused64: the fp64 chain;
 // Generic: layer by layer (generic.hip) -- any shape, and what a family that declines a call (BAMD_ERR_UNSUPPORTED) falls back to.
-enum class Family { PjConv, Bf16, F16, Fpga, Fused, Fused64, Generic };
+enum class Family { PjConv, Bf16, F16, F16X3, Fpga, Fused, Fused64, Generic };
 
 // encode / decode / forward + loss: the handle alone decides
 Family infer_family(const bamd_handle *h) {
     if (h->pj_state) return Family::PjConv;
     if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return Family::Bf16;
     if (h->mode == BAMD_MODE_F16 && h->bf16_state) return Family::F16;
+    if (h->mode == BAMD_MODE_F16X3 && h->f16x3_state) return Family::F16X3;
     if (h->fpga_state) return Family::Fpga;
     if (h->fused_ok) return Family::Fused;
     if (h->mode == BAMD_MODE_F64 && h->fused64_state) return Family::Fused64;
@@ -90,6 +92,10 @@ Family train_family(const bamd_handle *h, int64_t n_rows) {
     return Family::Generic;
 }
 
+// (4 is not a mode: BAMD_MODE_F16X3 is 5, see include/baler_amd.h)
+bool known_mode(int mode) {
+    return mode == BAMD_MODE_F32 || mode == BAMD_MODE_F64 || mode == BAMD_MODE_BF16 || mode == BAMD_MODE_F16 || mode == BAMD_MODE_F16X3;
+}
 bool quiet() { const char *q = getenv("BALER_AMD_QUIET"); return q && q[0] == '1'; }      // BALER_AMD_QUIET=1: no notices on stderr
 std::string dims_string(const bamd_handle *h) {      // "24-200-100-50-15-50-100-200-24"
     std::string d;
@@ -161,7 +167,7 @@ int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device
     BAMD_REQUIRE(dims && out, "null argument");
     BAMD_REQUIRE(n_layers >= 2 && n_layers % 2 == 0, "n_layers must be even and >= 2");
     BAMD_REQUIRE(act == BAMD_ACT_LEAKY_RELU || act == BAMD_ACT_RELU, "unknown activation");
-    BAMD_REQUIRE(mode == BAMD_MODE_F32 || mode == BAMD_MODE_F64 || mode == BAMD_MODE_BF16 || mode == BAMD_MODE_F16, "unknown mode");
+    BAMD_REQUIRE(known_mode(mode), "unknown mode");
     for (int l = 0; l <= n_layers; ++l) BAMD_REQUIRE(dims[l] > 0, "layer widths must be positive");
     DeviceGuard guard;
     if (int rc = open_device(__func__, device, guard)) return rc;
@@ -186,8 +192,9 @@ int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device
     // 192-209, other than the instantiated ones): the handle computes in float32 on whatever serves the shape there (run-time-width
     // classes, layer-wise kernels) and says so; bamd_mode_of() then reports BAMD_MODE_F32.  A slower path, not an error.
     bool demoted = false;
-    if ((mode == BAMD_MODE_BF16 && !bf16_has_kernels(h) && !fused_has_bf16_kernels(h)) || (mode == BAMD_MODE_F16 && !bf16_has_kernels(h))) {
-        h->mode = BAMD_MODE_F32;      // (BAMD_MODE_F16 follows the same rule; it has no wide-model kernels)
+    if ((mode == BAMD_MODE_BF16 && !bf16_has_kernels(h) && !fused_has_bf16_kernels(h)) || (mode == BAMD_MODE_F16 && !bf16_has_kernels(h)) ||
+        (mode == BAMD_MODE_F16X3 && !f16x3_has_kernels(h))) {
+        h->mode = BAMD_MODE_F32;      // (BAMD_MODE_F16 / BAMD_MODE_F16X3 follow the same rule; they have no wide-model kernels)
         demoted = true;
     }
     int rc = h->params.ensure((size_t)(h->nparams + 1) * h->esize);
@@ -200,12 +207,14 @@ int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device
         if (!rc) rc = bf16_train_setup(h);
     }
     if (!rc && h->mode == BAMD_MODE_F16) rc = bf16_setup(h);      // binary16 inference fragments beside the fused fp32 state it trains on
+    if (!rc && h->mode == BAMD_MODE_F16X3) rc = f16x3_setup(h);   // hi / lo binary16 fragments beside the same
     if (rc) { bamd_destroy(h); return rc; }
     *out = h;
     const int path = bamd_path_of(h);
     if (demoted && !quiet())
         fprintf(stderr, "[baler_amd] model %s: %s only; this handle computes in float32 (%s)\n", dims_string(h).c_str(),
                 mode == BAMD_MODE_F16 ? "BAMD_MODE_F16 has kernels for the 24-column AE with LeakyReLU"
+                : mode == BAMD_MODE_F16X3 ? "BAMD_MODE_F16X3 has kernels for the 24-column AE with LeakyReLU"
                                       : "BAMD_MODE_BF16 has kernels for the 24-column AE and the 2500-25 / 625-7 / 512-6 wide models",
                 path == BAMD_PATH_GENERIC ? "layer-wise kernels" : infer_family(h) == Family::Fpga ? "fused FPGA_prototype_model kernels" : "fused run-time-width kernels");
     if ((path == BAMD_PATH_GENERIC || path == BAMD_PATH_FUSED_INFER) && !quiet()) {
@@ -222,7 +231,7 @@ int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device
 int bamd_create_pjconv(int z_dim, int mode, int device, bamd_handle **out) {
     BAMD_REQUIRE(out, "null argument");
     BAMD_REQUIRE(z_dim >= 1 && z_dim <= 2450, "PJ_Conv_AE latent size must be in 1..2450 (encoder.5 = Linear(500, z), decoder.0 = Linear(z, 500))");
-    BAMD_REQUIRE(mode == BAMD_MODE_F32 || mode == BAMD_MODE_F64 || mode == BAMD_MODE_BF16 || mode == BAMD_MODE_F16, "unknown mode");
+    BAMD_REQUIRE(known_mode(mode), "unknown mode");
     if (mode == BAMD_MODE_F64) {
         set_error("bamd_create_pjconv: PJ_Conv_AE computes in float32 only (the reference model's parameters and 2-D data are float32, "
                   "training.py:222-227, helper.py:556-558); BAMD_MODE_F64 is not supported");
@@ -247,6 +256,9 @@ int bamd_create_pjconv(int z_dim, int mode, int device, bamd_handle **out) {
     if (mode == BAMD_MODE_F16 && !quiet())
         fprintf(stderr, "[baler_amd] model PJ_Conv_AE(z=%d): BAMD_MODE_F16 has kernels for the 24-column AE with LeakyReLU only; this "
                         "handle computes in float32 (fused PJ_Conv_AE kernels)\n", z_dim);
+    if (mode == BAMD_MODE_F16X3 && !quiet())
+        fprintf(stderr, "[baler_amd] model PJ_Conv_AE(z=%d): BAMD_MODE_F16X3 has kernels for the 24-column AE with LeakyReLU only; this "
+                        "handle computes in float32 (fused PJ_Conv_AE kernels)\n", z_dim);
     *out = h;
     return BAMD_OK;
 }
@@ -256,6 +268,7 @@ int bamd_path_of(const bamd_handle *h) {
     switch (infer_family(h)) {
     case Family::Bf16: return BAMD_PATH_BF16;
     case Family::F16: return BAMD_PATH_F16;
+    case Family::F16X3: return BAMD_PATH_F16X3;
     case Family::Fused: return fused_trains(h) ? BAMD_PATH_FUSED : BAMD_PATH_FUSED_INFER;
     case Family::Generic: return BAMD_PATH_GENERIC;
     default: return BAMD_PATH_FUSED;
@@ -271,6 +284,7 @@ void bamd_destroy(bamd_handle *h) {
     fpga_teardown(h);
     pj_teardown(h);
     bf16_teardown(h);
+    f16x3_teardown(h);
     bf16_train_teardown(h);
     comm_teardown(h);
     h->params.release();
@@ -308,6 +322,10 @@ int bamd_load_params(bamd_handle *h, const void *params, int dtype, void *stream
         rc = bf16_pack(h, s);
         h->bf16_infer_stale = false;
         return rc ? rc : fused_pack(h, s);
+    case Family::F16X3:                              // the split inference fragments and the fp32 fragments it trains on
+        rc = f16x3_pack(h, s);
+        h->bf16_infer_stale = false;
+        return rc ? rc : fused_pack(h, s);
     default:
         // a handle may train on another family than it infers on, so this packs by compute type, not by route (no-ops without the state)
         return h->mode == BAMD_MODE_F64 ? fused64_pack(h, s) : fused_pack(h, s);
@@ -340,6 +358,7 @@ int bamd_renormalize(const void *x, int dtype, int64_t n_rows, int n_cols, const
 // Family::Bf16 re-rounds its fragments on demand: a training step refreshes only what the next step reads, inference lags (lazily)
 static int bf16_train_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h->bf16_train_stale, false) ? bf16_train_pack(h, s) : BAMD_OK; }
 static int bf16_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h->bf16_infer_stale, false) ? bf16_pack(h, s) : BAMD_OK; }
+static int f16x3_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h->bf16_infer_stale, false) ? f16x3_pack(h, s) : BAMD_OK; }
 
 // Every path that has just written h->params / h->packed (the Adam kernel, or Adam inside a weight-gradient launch) ends here: lazily
 // refreshed float32 copies are stale, and a BF16 handle's bf16 fragments are re-rounded (on demand where the handle has both sets).
@@ -350,7 +369,7 @@ static int params_stepped(bamd_handle *h, hipStream_t s) {
         if (bf16_train_ok(h)) { h->bf16_infer_stale = true; h->bf16_train_stale = true; }
         else return bf16_pack(h, s);
     }
-    if (infer_family(h) == Family::F16) h->bf16_infer_stale = true;      // re-rounded by the next inference call
+    if (infer_family(h) == Family::F16 || infer_family(h) == Family::F16X3) h->bf16_infer_stale = true;      // re-rounded / re-split by the next inference call
     return BAMD_OK;
 }
 
@@ -377,6 +396,11 @@ static int infer_rows(bamd_handle *h, InferKind kind, const void *in, int in_dty
         if (kind == K_ENCODE) return bf16_encode(h, in, in_dtype, n, features, out, out_dtype, s);
         if (kind == K_DECODE) return bf16_decode(h, in, in_dtype, n, renorm, int_mask, out, out_dtype, s);
         return bf16_forward_loss(h, in, in_dtype, n, features, out, out_dtype, loss_sum, s);
+    case Family::F16X3:
+        if ((rc = f16x3_sync(h, s))) return rc;
+        if (kind == K_ENCODE) return f16x3_encode(h, in, in_dtype, n, features, out, out_dtype, s);
+        if (kind == K_DECODE) return f16x3_decode(h, in, in_dtype, n, renorm, int_mask, out, out_dtype, s);
+        return f16x3_forward_loss(h, in, in_dtype, n, features, out, out_dtype, loss_sum, s);
     case Family::Fpga:
         return fpga_infer(h, kind, in, in_dtype, n, features, out, out_dtype, renorm, int_mask, loss_sum, s);
     case Family::Fused:
@@ -399,7 +423,7 @@ static int infer_rows(bamd_handle *h, InferKind kind, const void *in, int in_dty
 // launch -- the same rounding (float32 first, then 16 bits) and the same exact widening, so the results are bit-identical either way.
 static bool latent_in_kernel(const bamd_handle *h) {
     const Family f = infer_family(h);      // (Fused: the register chain; the wide-layer kernels: workspace)
-    return f == Family::Bf16 || f == Family::F16 || f == Family::Generic || (f == Family::Fused && fused_latent_in_kernel(h));
+    return f == Family::Bf16 || f == Family::F16 || f == Family::F16X3 || f == Family::Generic || (f == Family::Fused && fused_latent_in_kernel(h));
 }
 int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features, void *z,
                 int z_dtype, void *stream) {
@@ -466,7 +490,8 @@ static int fwd_bwd_rows(bamd_handle *h, Family fam, const void *x, int x_dtype, 
     case Family::Fused64:      // small batches: fp64 chain + weight-gradient tiles; otherwise the layer-wise kernels
         rc = fused64_step(h, x, x_dtype, n_rows, features, grads, nullptr, nullptr, nullptr, nullptr, nullptr, s);
         break;
-    case Family::F16:      // an inference family: train_family() never returns it
+    case Family::F16:      // inference families: train_family() never returns them
+    case Family::F16X3:
     case Family::Generic: break;
     }
     if (rc != BAMD_ERR_UNSUPPORTED) return rc;
@@ -538,7 +563,7 @@ int bamd_train_step(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, 
             return fpga_step(h, x, x_dtype, n_rows, features, nullptr, grads, params, m, v, hp, loss_accum, s);
         case Family::Fused:       // small batches: Adam (+ re-pack) in the weight-gradient launch
             rc = fused_train_step(h, x, x_dtype, n_rows, features, grads, params, m, v, *hp, loss_accum, s);
-            if (rc == BAMD_OK && (h->mode == BAMD_MODE_BF16 || h->mode == BAMD_MODE_F16)) rc = params_stepped(h, s);
+            if (rc == BAMD_OK && (h->mode == BAMD_MODE_BF16 || h->mode == BAMD_MODE_F16 || h->mode == BAMD_MODE_F16X3)) rc = params_stepped(h, s);
             break;
         case Family::Fused64: rc = fused64_step(h, x, x_dtype, n_rows, features, grads, params, m, v, hp, loss_accum, s); break;
         default: break;      // Bf16, Generic: no step of their own

@@ -85,6 +85,7 @@ struct bamd_handle {
     bamd::DevBuf packed_small;      // ... and its fragment-packed weights (fused.hip: SmallScope swaps both in for a small-batch call)
     void *fused64_state = nullptr;  // maps + packed fp64 weights of the fp64 small-batch step (fused64.hip)
     void *bf16_state = nullptr;     // packed 16-bit weights + maps of the bf16 / f16 inference mode (bf16.hip; the mode decides the element type)
+    void *f16x3_state = nullptr;    // hi / lo binary16 fragments + maps of the fp16x3 inference mode (f16x3.hip); stale with bf16_infer_stale
     void *bf16_train_state = nullptr;   // packed bf16 weights + maps of the bf16 training kernels (bf16_train.hip)
     bool bf16_infer_stale = false;  // the inference fragments lag h->params (re-packed lazily by the next inference call)
     bool bf16_train_stale = false;  // the bf16 TRAINING fragments lag h->params (re-packed by the next bf16 training launch)
@@ -96,7 +97,7 @@ struct bamd_handle {
 
     int param_dtype() const { return esize == 8 ? BAMD_F64 : BAMD_F32; }   // bamd_dtype of params, grads, m and v
     bool has_act(int l) const { return !(l == L / 2 - 1 || l == L - 1); }
-    bool f32_compute() const { return mode == BAMD_MODE_F32 || mode == BAMD_MODE_F16; }   // an F16 handle is an F32 handle outside its inference kernels
+    bool f32_compute() const { return mode == BAMD_MODE_F32 || mode == BAMD_MODE_F16 || mode == BAMD_MODE_F16X3; }   // F16 / F16X3 handles are F32 handles outside their inference kernels
     bool leaky() const { return act == BAMD_ACT_LEAKY_RELU; }   // the fused / fp64 / bf16 families implement LeakyReLU(0.01) only
 };
 

@@ -20,4 +20,16 @@ void bf16_train_teardown(bamd_handle *h);
 bool bf16_train_ok(const bamd_handle *h);
 int bf16_train_pack(bamd_handle *h, hipStream_t s);   // h->params (fp32) -> the training kernels' bf16 fragments
 int bf16_fwd_bwd(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *grads, hipStream_t s);
+// fp16x3 inference mode (f16x3.hip, BAMD_MODE_F16X3): the same three calls at fp32 accuracy, every fp32 operand split into two binary16
+// values and three v_mfma_f32_16x16x32_f16 products per tile.  One state per handle (h->f16x3_state); the shapes of bf16_has_kernels.
+bool f16x3_has_kernels(const bamd_handle *h);
+int f16x3_setup(bamd_handle *h);                 // BAMD_ERR_UNSUPPORTED for shapes without an instantiation
+int f16x3_pack(bamd_handle *h, hipStream_t s);   // h->params (fp32) -> hi / lo binary16 fragments + fp32 bias fragments
+void f16x3_teardown(bamd_handle *h);
+int f16x3_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype,
+                 hipStream_t s);
+int f16x3_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features, const uint8_t *int_mask,
+                 void *out, int out_dtype, hipStream_t s);
+int f16x3_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *recon,
+                       int recon_dtype, double *loss_sum, hipStream_t s);
 }  // namespace bamd

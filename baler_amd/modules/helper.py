@@ -361,18 +361,19 @@ def _check_float16_range(h, flat, feats, out, world):
 
 
 def _check_fp16_mode_range(h, rows_in, rows_out, world, what):
-    """The fp16 compute mode (BAMD_MODE_F16: binary16 layer inputs, include/baler_amd.h): a value beyond +-65504 inside the chain turns
-    every output of ITS row non-finite.  Count, on the device, the rows whose input is entirely finite but whose output is not (rows
-    that came in with NaN / inf pass through as in every mode) and refuse to go on if there are any.  Every rank takes part and
-    every rank raises.  Handles that compute in another mode are not checked."""
-    if h.compute_mode != native.MODE_F16:
+    """The fp16 and fp16x3 compute modes (BAMD_MODE_F16 / BAMD_MODE_F16X3: binary16 layer inputs, include/baler_amd.h): a value beyond
+    +-65504 inside the chain turns every output of ITS row non-finite.  Count, on the device, the rows whose input is entirely finite
+    but whose output is not (rows that came in with NaN / inf pass through as in every mode) and refuse to go on if there are any.
+    Every rank takes part and every rank raises.  Handles that compute in another mode are not checked."""
+    if h.compute_mode not in (native.MODE_F16, native.MODE_F16X3):
         return
     bad = (torch.isfinite(rows_in).all(dim=1) & ~torch.isfinite(rows_out).all(dim=1)).sum().to(torch.float64).reshape(1)
     if world > 1:
         bdist.allreduce_sum(bad)
     count = int(bad.item())
     if count:
-        raise ValueError(f"BALER_AMD_MODE=fp16: {count} rows with finite input left the float16 range (|value| > 65504) inside the "
+        name = "fp16" if h.compute_mode == native.MODE_F16 else "fp16x3"
+        raise ValueError(f"BALER_AMD_MODE={name}: {count} rows with finite input left the float16 range (|value| > 65504) inside the "
                          f"model and {what} to non-finite values; nothing is written.  Use the bf16 mode (BALER_AMD_MODE=bf16: "
                          "float32's range at 8 bits of precision) or the fp32 mode (BALER_AMD_MODE=fp32) for this model and data.")
 

@@ -14,7 +14,7 @@ Protocol kept: ctor ``(n_features, z_dim)``, ``encode / decode / forward``, ``st
 parameters live in ONE flat device tensor in state-dict order and every forward/backward is a
 hand-written HIP kernel behind the C ABI (``baler_amd/native.py``).  torch is the tensor container.
 
-Compute mode (``fp32`` parity mode by default, ``fp64``, ``bf16``, ``fp16``) comes from
+Compute mode (``fp32`` parity mode by default, ``fp64``, ``bf16``, ``fp16``, ``fp16x3``) comes from
 ``BALER_AMD_MODE`` or ``set_default_mode``; the state dict keeps the reference's dtype either way.
 """
 import math

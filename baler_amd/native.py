@@ -16,7 +16,10 @@ LIB_PATH = os.environ.get("BALER_AMD_LIB", os.path.join(_HERE, "libbaler_amd.so"
 F32, F64 = 0, 1
 F16, BF16 = 2, 3        # 16-bit latent codes: the z of bamd_encode / bamd_decode only (include/baler_amd.h, bamd_dtype)
 MODE_F32, MODE_F64, MODE_BF16, MODE_F16 = 0, 1, 2, 3      # MODE_F16: binary16 inference of the 24-column AE, fp32 training
-MODE_NAMES = {"fp32": MODE_F32, "f32": MODE_F32, "fp64": MODE_F64, "f64": MODE_F64, "bf16": MODE_BF16, "fp16": MODE_F16, "f16": MODE_F16}
+MODE_F16X3 = 5      # fp32 accuracy from three binary16 MFMA products per tile (24-column AE inference, fp32 training); 4 is not a mode
+MODE_NAMES = {"fp32": MODE_F32, "f32": MODE_F32, "fp64": MODE_F64, "f64": MODE_F64, "bf16": MODE_BF16, "fp16": MODE_F16, "f16": MODE_F16,
+              "fp16x3": MODE_F16X3, "f16x3": MODE_F16X3}
+PATH_NAMES = {0: "generic", 1: "fused", 2: "bf16", 3: "fused-infer", 4: "f16", 5: "f16x3"}      # bamd_path
 ACT_LEAKY_RELU, ACT_RELU = 0, 1
 ACT_NAMES = {"leaky_relu": ACT_LEAKY_RELU, "relu": ACT_RELU}
 
@@ -383,13 +386,13 @@ class Handle:
         self._h = h
         self.nparams = int(lib().bamd_param_count(h))
         self.param_dtype = torch.float64 if self.mode == MODE_F64 else torch.float32
-        # the mode the library computes in: "bf16" / "fp16" asked of a shape without such kernels is served in float32 (notice on stderr)
+        # the mode the library computes in: "bf16" / "fp16" / "fp16x3" asked of a shape without such kernels is served in float32 (notice on stderr)
         self.compute_mode = int(lib().bamd_mode_of(h))
 
     @classmethod
     def pj_conv(cls, z_dim, mode="fp32", device=None):
         """Handle of PJ_Conv_AE (bamd_create_pjconv): rows of 784 values (one 28 x 28 frame each) in and out, latent z_dim
-        (1..2450); every row-based method works unchanged.  "bf16" / "fp16" compute in float32 (notice on stderr), "fp64" is refused."""
+        (1..2450); every row-based method works unchanged.  "bf16" / "fp16" / "fp16x3" compute in float32 (notice on stderr), "fp64" is refused."""
         require_gpu()
         self = cls.__new__(cls)
         self.dims = [PJ_FEATURES, int(z_dim), PJ_FEATURES]
@@ -434,9 +437,9 @@ class Handle:
 
     @property
     def path(self):
-        """"fused" | "bf16" | "f16" | "generic" | "fused-infer" (fused encode / decode / validation, layer-wise training): which
+        """"fused" | "bf16" | "f16" | "f16x3" | "generic" | "fused-infer" (fused encode / decode / validation, layer-wise training): which
         kernels serve this shape's throughput calls (bamd_path_of)."""
-        return {0: "generic", 1: "fused", 2: "bf16", 3: "fused-infer", 4: "f16"}[int(lib().bamd_path_of(self._h))]
+        return PATH_NAMES[int(lib().bamd_path_of(self._h))]
 
     def load_params(self, flat):
         flat = _dev_tensor(flat)

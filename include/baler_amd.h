@@ -138,8 +138,33 @@ typedef enum bamd_dtype { BAMD_F32 = 0, BAMD_F64 = 1, BAMD_F16 = 2, BAMD_BF16 = 
  * kernels a BAMD_MODE_F32 handle of the same shape runs, at every batch size, with bit-identical results (params / m / v / grads
  * are FLOAT); the binary16 fragments are re-rounded lazily after an optimiser step or bamd_load_params; bamd_activation_means runs
  * on the fp32 layer-wise kernels.  Any shape without F16 kernels (other column counts, the wide models, BAMD_ACT_RELU handles,
+ * PJ_Conv_AE) is created as a float32 handle with one notice on stderr, and bamd_mode_of() returns BAMD_MODE_F32.
+ * F16X3 = three v_mfma_f32_16x16x32_f16 products per tile with fp32 accumulation: a PARITY mode for INFERENCE -- the accuracy of F32
+ * (the measurements are in DESIGN.md section 15) on the binary16 MFMA.  It serves
+ * bamd_encode, bamd_decode and bamd_forward_loss of the 24-column AE at every fused latent size (15, 12, 10, 8, 6, 5, 4, 3, 2).
+ * (Its value is 5: 4 is not a mode and stays refused as "unknown mode".)  Arithmetic:
+ *   Split.  An fp32 value a becomes two binary16 values: hi = binary16(a), round to nearest even, NO clamp; lo = binary16((a - hi) *
+ *   2^11).  a - hi is exact in fp32 and the scale is a power of two, so lo does not depend on the instructions that compute it.
+ *   Weights are split from the fp32 master copy when they are packed.  Biases stay fp32.
+ *   Layer.  main = b + sum hi_w * hi_h (the bias is the start value); corr = sum (lo_w * hi_h + hi_w * lo_h); both are fp32
+ *   accumulators of the MFMA, whose summation order is unspecified; a = main + corr * 2^-11 in fp32, rounded once (corr * 2^-11 is
+ *   exact).  The lo * lo product (2^-22 of the result) is not computed.
+ *   Activated layers.  LeakyReLU is max(a, a * 0.01f) on the fp32 value; the value is split AFTER the activation (the order of the
+ *   BF16 kernels, not of the F16 mode).
+ *   Rows are normalised in float64 when features are given, rounded ONCE to float32, then split.  Latent codes on bamd_decode:
+ *   float32 / float64 codes are rounded to float32, then split; BAMD_F16 and BAMD_BF16 codes widen exactly to float32 and are split
+ *   like any float32 value -- a binary16 code (and a bfloat16 code inside binary16's normal range) has lo = 0 --, so decoding 16-bit
+ *   codes and decoding their float32 widening give the same bits.  bamd_forward_loss is the encode, then the decode of the UNROUNDED
+ *   fp32 latent.  The latent and the reconstruction stay fp32 and go through the epilogues of the BF16 mode (un-normalise + int
+ *   truncation, loss partials, every z_dtype).  Results are bitwise repeatable.
+ *   Range: binary16's.  A value whose hi part lies beyond 65504 (a row element, a latent code, an activation) becomes +-inf and
+ *   every output of THAT ROW becomes non-finite; no other row changes.  A WEIGHT beyond 65504 does that to every row.  baler_amd's
+ *   compress / decompress count such rows on the device and refuse before writing, as in the F16 mode.
+ * Everything else on an F16X3 handle is exact fp32, as on an F16 handle: the training calls, bamd_adam_step and
+ * bamd_activation_means run the launches of a BAMD_MODE_F32 handle bit for bit; the split fragments are re-made lazily after an
+ * optimiser step or bamd_load_params.  Any shape without F16X3 kernels (other column counts, the wide models, BAMD_ACT_RELU handles,
  * PJ_Conv_AE) is created as a float32 handle with one notice on stderr, and bamd_mode_of() returns BAMD_MODE_F32. */
-typedef enum bamd_mode { BAMD_MODE_F32 = 0, BAMD_MODE_F64 = 1, BAMD_MODE_BF16 = 2, BAMD_MODE_F16 = 3 } bamd_mode;
+typedef enum bamd_mode { BAMD_MODE_F32 = 0, BAMD_MODE_F64 = 1, BAMD_MODE_BF16 = 2, BAMD_MODE_F16 = 3, BAMD_MODE_F16X3 = 5 } bamd_mode;
 
 /* Adam hyper-parameters of one step (torch.optim.Adam defaults are beta1=.9 beta2=.999 eps=1e-8). */
 typedef struct bamd_adam {
@@ -173,7 +198,7 @@ typedef enum bamd_act {
  * de1 and de2.  ReLU follows torch: relu(nan) = nan, relu(-inf) = 0, and the backward pass lets the gradient through where the
  * layer's output is > 0 (threshold_backward; an exact-zero pre-activation gets a zero gradient).  A BAMD_ACT_RELU handle runs on the
  * fused FPGA_prototype_model kernels (fpga.hip) for n_features <= 64 and z <= 32 in BAMD_MODE_F32 / BAMD_MODE_F64, and on the
- * layer-wise kernels for every other shape; the LeakyReLU kernel families never serve it.  In BAMD_MODE_BF16 / BAMD_MODE_F16 it is created as a
+ * layer-wise kernels for every other shape; the LeakyReLU kernel families never serve it.  In BAMD_MODE_BF16 / BAMD_MODE_F16 / BAMD_MODE_F16X3 it is created as a
  * float32 handle with a notice on stderr.  The activation-means diagnostic returns BAMD_ERR_UNSUPPORTED for it (the reference model
  * has no activation hooks either, training.py:287). */
 int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device, bamd_handle **out);
@@ -191,7 +216,7 @@ int bamd_act_of(const bamd_handle *h);     /* the handle's bamd_act, or BAMD_ERR
  * parameters.  The loss of bamd_forward_loss / bamd_fwd_bwd is utils.mse_sum_loss_l1(validate=True) (utils.py:176-211) of the
  * reference's 2-D path, whose divisor is true_data.shape[1] = the channel count, 1: the PLAIN sum of squared errors, not divided by 784.
  * Arithmetic: v_mfma_f32_16x16x4_f32 (exact fp32) implicit GEMMs, fixed-order weight-gradient sums: bitwise repeatable.
- * z_dim: 1 .. 2450 (else BAMD_ERR_INVALID).  mode: BAMD_MODE_F32; BAMD_MODE_BF16 / BAMD_MODE_F16 give a float32 handle with a notice on stderr
+ * z_dim: 1 .. 2450 (else BAMD_ERR_INVALID).  mode: BAMD_MODE_F32; BAMD_MODE_BF16 / BAMD_MODE_F16 / BAMD_MODE_F16X3 give a float32 handle with a notice on stderr
  * (bamd_mode_of() reports BAMD_MODE_F32); BAMD_MODE_F64 returns BAMD_ERR_UNSUPPORTED.  Served on such a handle: bamd_encode,
  * bamd_decode (with the un-normalise / int-mask epilogue), bamd_forward_loss, bamd_fwd_bwd, bamd_adam_step, bamd_train_step,
  * bamd_train_epoch, bamd_train_epoch_dp (and the communicator calls), bamd_load_params, bamd_param_count, bamd_path_of
@@ -228,11 +253,12 @@ typedef enum bamd_path {
     BAMD_PATH_BF16 = 2,      /* bf16.hip / bf16_train.hip (24-column AE, BAMD_MODE_BF16); its small batches use the fused fp32 step */
     BAMD_PATH_FUSED_INFER = 3, /* 64..127 columns with BALER_AMD_MID_HYBRID=0 or BALER_AMD_WIDE_CLASS=0: fused.hip for encode / decode / forward + loss and
                               * the small-batch training kernels (larger batches chunk after chunk on the same kernels) */
-    BAMD_PATH_F16 = 4        /* bf16.hip's binary16 instantiations for inference (24-column AE, BAMD_MODE_F16); training on the fused fp32 kernels */
+    BAMD_PATH_F16 = 4,       /* bf16.hip's binary16 instantiations for inference (24-column AE, BAMD_MODE_F16); training on the fused fp32 kernels */
+    BAMD_PATH_F16X3 = 5      /* f16x3.hip: split-binary16 inference at fp32 accuracy (24-column AE, BAMD_MODE_F16X3); training on the fused fp32 kernels */
 } bamd_path;
 int bamd_path_of(const bamd_handle *h);   /* a bamd_path, or BAMD_ERR_INVALID for a null handle */
 int64_t bamd_param_count(const bamd_handle *h);
-int bamd_mode_of(const bamd_handle *h);    /* the mode the handle COMPUTES in (BAMD_MODE_BF16 / BAMD_MODE_F16 asked of a shape without such kernels: BAMD_MODE_F32) */
+int bamd_mode_of(const bamd_handle *h);    /* the mode the handle COMPUTES in (BAMD_MODE_BF16 / BAMD_MODE_F16 / BAMD_MODE_F16X3 asked of a shape without such kernels: BAMD_MODE_F32) */
 
 /* (Re)build the handle's MFMA-fragment-packed weight copy from the caller's flat parameter vector
  * (device pointer; dtype F32 or F64).  Call after loading a checkpoint or changing params outside
