@@ -56,16 +56,15 @@ struct DeviceGuard {
 // ---- the kernel families: their precedence is written down HERE, once for inference and once for training, and every entry point
 // below switches on one of the two routes (a new family is added there).  PjConv: pjconv.hip; Bf16: bf16.hip,
 // bf16_train.hip; F16: the binary16 instantiations of bf16.hip (inference only: such a handle TRAINS on Fused, like an F32 handle); F16X3: f16x3.hip
-// (inference only, like F16); Fpga: fpga.hip; Fused: the fp32 register chain and wide-layer kernels of fused.hip; Fused64: the fp64 chain;
+// (inference only, like F16) -- these three infer through ONE state and one set of entry points (bf16.hpp), where the mode has named
+// the kernels at setup; Fpga: fpga.hip; Fused: the fp32 register chain and wide-layer kernels of fused.hip; Fused64: the fp64 chain;
 // Generic: layer by layer (generic.hip) -- any shape, and what a family that declines a call (BAMD_ERR_UNSUPPORTED) falls back to.
 enum class Family { PjConv, Bf16, F16, F16X3, Fpga, Fused, Fused64, Generic };
 
 // encode / decode / forward + loss: the handle alone decides
 Family infer_family(const bamd_handle *h) {
     if (h->pj_state) return Family::PjConv;
-    if (h->mode == BAMD_MODE_BF16 && h->bf16_state) return Family::Bf16;
-    if (h->mode == BAMD_MODE_F16 && h->bf16_state) return Family::F16;
-    if (h->mode == BAMD_MODE_F16X3 && h->f16x3_state) return Family::F16X3;
+    if (h->infer16_state) return h->mode == BAMD_MODE_BF16 ? Family::Bf16 : h->mode == BAMD_MODE_F16 ? Family::F16 : Family::F16X3;
     if (h->fpga_state) return Family::Fpga;
     if (h->fused_ok) return Family::Fused;
     if (h->mode == BAMD_MODE_F64 && h->fused64_state) return Family::Fused64;
@@ -203,11 +202,10 @@ int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device
     if (!rc) rc = fused64_setup(h);
     if (!rc) rc = fpga_setup(h);
     if (!rc && h->mode == BAMD_MODE_BF16 && !fused_serves_bf16_inference(h)) {   // (wide models in the bf16 mode are served by fused.hip)
-        rc = bf16_setup(h);
+        rc = infer16_setup(h);
         if (!rc) rc = bf16_train_setup(h);
     }
-    if (!rc && h->mode == BAMD_MODE_F16) rc = bf16_setup(h);      // binary16 inference fragments beside the fused fp32 state it trains on
-    if (!rc && h->mode == BAMD_MODE_F16X3) rc = f16x3_setup(h);   // hi / lo binary16 fragments beside the same
+    if (!rc && (h->mode == BAMD_MODE_F16 || h->mode == BAMD_MODE_F16X3)) rc = infer16_setup(h);   // binary16 / hi | lo inference fragments beside the fused fp32 state it trains on
     if (rc) { bamd_destroy(h); return rc; }
     *out = h;
     const int path = bamd_path_of(h);
@@ -283,8 +281,7 @@ void bamd_destroy(bamd_handle *h) {
     fused64_teardown(h);
     fpga_teardown(h);
     pj_teardown(h);
-    bf16_teardown(h);
-    f16x3_teardown(h);
+    infer16_teardown(h);
     bf16_train_teardown(h);
     comm_teardown(h);
     h->params.release();
@@ -312,20 +309,16 @@ int bamd_load_params(bamd_handle *h, const void *params, int dtype, void *stream
     h->params_loaded = true;
     switch (infer_family(h)) {
     case Family::PjConv: return BAMD_OK;             // the PJ_Conv_AE kernels read the flat copy itself
-    case Family::Bf16:                               // several families: the bf16, the bf16-training and the fp32 small-batch fragments
-        rc = bf16_pack(h, s);
-        h->bf16_infer_stale = false;
-        h->bf16_train_stale = false;
-        if (!rc) rc = bf16_train_pack(h, s);
-        return rc ? rc : fused_pack(h, s);           // fp32 fragments of the small-batch kernels (no-op without them)
-    case Family::F16:                                // the binary16 inference fragments and the fp32 fragments it trains on
-        rc = bf16_pack(h, s);
-        h->bf16_infer_stale = false;
-        return rc ? rc : fused_pack(h, s);
-    case Family::F16X3:                              // the split inference fragments and the fp32 fragments it trains on
-        rc = f16x3_pack(h, s);
-        h->bf16_infer_stale = false;
-        return rc ? rc : fused_pack(h, s);
+    case Family::Bf16:
+    case Family::F16:
+    case Family::F16X3:                              // several families: the 16-bit inference fragments, ...
+        rc = infer16_pack(h, s);
+        h->infer16_stale = false;
+        if (h->mode == BAMD_MODE_BF16) {             // ... the bf16 training fragments, ...
+            h->bf16_train_stale = false;
+            if (!rc) rc = bf16_train_pack(h, s);
+        }
+        return rc ? rc : fused_pack(h, s);           // ... and the fp32 fragments the handle trains on (Bf16: its small batches; a no-op without them)
     default:
         // a handle may train on another family than it infers on, so this packs by compute type, not by route (no-ops without the state)
         return h->mode == BAMD_MODE_F64 ? fused64_pack(h, s) : fused_pack(h, s);
@@ -355,10 +348,10 @@ int bamd_renormalize(const void *x, int dtype, int64_t n_rows, int n_cols, const
     return launch_renormalize(x, dtype, n_rows, n_cols, features, int_mask, out, (hipStream_t)stream);
 }
 
-// Family::Bf16 re-rounds its fragments on demand: a training step refreshes only what the next step reads, inference lags (lazily)
+// Family::Bf16 re-rounds its fragments on demand: a training step refreshes only what the next step reads, inference lags (lazily);
+// F16 / F16X3 have inference fragments only
 static int bf16_train_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h->bf16_train_stale, false) ? bf16_train_pack(h, s) : BAMD_OK; }
-static int bf16_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h->bf16_infer_stale, false) ? bf16_pack(h, s) : BAMD_OK; }
-static int f16x3_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h->bf16_infer_stale, false) ? f16x3_pack(h, s) : BAMD_OK; }
+static int infer16_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h->infer16_stale, false) ? infer16_pack(h, s) : BAMD_OK; }
 
 // Every path that has just written h->params / h->packed (the Adam kernel, or Adam inside a weight-gradient launch) ends here: lazily
 // refreshed float32 copies are stale, and a BF16 handle's bf16 fragments are re-rounded (on demand where the handle has both sets).
@@ -366,10 +359,10 @@ static int f16x3_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h->b
 static int params_stepped(bamd_handle *h, hipStream_t s) {
     fused_params_changed(h);
     if (infer_family(h) == Family::Bf16) {
-        if (bf16_train_ok(h)) { h->bf16_infer_stale = true; h->bf16_train_stale = true; }
-        else return bf16_pack(h, s);
+        if (bf16_train_ok(h)) { h->infer16_stale = true; h->bf16_train_stale = true; }
+        else return infer16_pack(h, s);
     }
-    if (infer_family(h) == Family::F16 || infer_family(h) == Family::F16X3) h->bf16_infer_stale = true;      // re-rounded / re-split by the next inference call
+    if (infer_family(h) == Family::F16 || infer_family(h) == Family::F16X3) h->infer16_stale = true;      // re-rounded / re-split by the next inference call
     return BAMD_OK;
 }
 
@@ -391,16 +384,12 @@ static int infer_rows(bamd_handle *h, InferKind kind, const void *in, int in_dty
         if (kind == K_DECODE) return pj_decode(h, in, in_dtype, n, renorm, int_mask, out, out_dtype, s);
         return pj_forward_loss(h, in, in_dtype, n, features, out, out_dtype, loss_sum, s);
     case Family::Bf16:
-    case Family::F16:      // the same entry points: the state's element type is the handle's
-        if ((rc = bf16_sync(h, s))) return rc;
-        if (kind == K_ENCODE) return bf16_encode(h, in, in_dtype, n, features, out, out_dtype, s);
-        if (kind == K_DECODE) return bf16_decode(h, in, in_dtype, n, renorm, int_mask, out, out_dtype, s);
-        return bf16_forward_loss(h, in, in_dtype, n, features, out, out_dtype, loss_sum, s);
-    case Family::F16X3:
-        if ((rc = f16x3_sync(h, s))) return rc;
-        if (kind == K_ENCODE) return f16x3_encode(h, in, in_dtype, n, features, out, out_dtype, s);
-        if (kind == K_DECODE) return f16x3_decode(h, in, in_dtype, n, renorm, int_mask, out, out_dtype, s);
-        return f16x3_forward_loss(h, in, in_dtype, n, features, out, out_dtype, loss_sum, s);
+    case Family::F16:
+    case Family::F16X3:    // the same entry points: the state's kernels are the mode's
+        if ((rc = infer16_sync(h, s))) return rc;
+        if (kind == K_ENCODE) return infer16_encode(h, in, in_dtype, n, features, out, out_dtype, s);
+        if (kind == K_DECODE) return infer16_decode(h, in, in_dtype, n, renorm, int_mask, out, out_dtype, s);
+        return infer16_forward_loss(h, in, in_dtype, n, features, out, out_dtype, loss_sum, s);
     case Family::Fpga:
         return fpga_infer(h, kind, in, in_dtype, n, features, out, out_dtype, renorm, int_mask, loss_sum, s);
     case Family::Fused:

@@ -36,6 +36,9 @@ void set_error(const std::string &msg);
         }                                                                                   \
     } while (0)
 #define BAMD_REQUIRE(cond, msg) BAMD_REQUIRE_AS(__func__, cond, msg)
+// The fused latent sizes of the 24-column AE: every kernel family that instantiates AE(24, Z) does so for X(Z) of this list
+// (fused.hip find_ops; bf16_net.hpp infer16_find)
+#define BAMD_AE24_LATENTS(X) X(15) X(12) X(10) X(8) X(6) X(5) X(4) X(3) X(2)
 // What an inference launch computes.  The kernel templates of fused.hip and fused64_infer.hpp take it as an int parameter with these values.
 enum InferKind : int { K_ENCODE = 0, K_DECODE = 1, K_FORWARD = 2 };
 
@@ -84,10 +87,9 @@ struct bamd_handle {
     void *fused_small = nullptr;    // 64..127-column tables: second fused state (small-batch class kernels) beside the wide class in fused_state
     bamd::DevBuf packed_small;      // ... and its fragment-packed weights (fused.hip: SmallScope swaps both in for a small-batch call)
     void *fused64_state = nullptr;  // maps + packed fp64 weights of the fp64 small-batch step (fused64.hip)
-    void *bf16_state = nullptr;     // packed 16-bit weights + maps of the bf16 / f16 inference mode (bf16.hip; the mode decides the element type)
-    void *f16x3_state = nullptr;    // hi / lo binary16 fragments + maps of the fp16x3 inference mode (f16x3.hip); stale with bf16_infer_stale
+    void *infer16_state = nullptr;  // Infer16State (bf16_net.hpp) of the bf16 / f16 / fp16x3 inference modes: maps + packed fragments; the mode decides whose
     void *bf16_train_state = nullptr;   // packed bf16 weights + maps of the bf16 training kernels (bf16_train.hip)
-    bool bf16_infer_stale = false;  // the inference fragments lag h->params (re-packed lazily by the next inference call)
+    bool infer16_stale = false;     // the fragments of infer16_state lag h->params (re-packed lazily by the next inference call)
     bool bf16_train_stale = false;  // the bf16 TRAINING fragments lag h->params (re-packed by the next bf16 training launch)
     void *comm = nullptr;           // ncclComm_t of data-parallel training (comm.hip); null: single process
     bool comm_owned = false;        // created by bamd_comm_init (destroyed with the handle) vs attached by the caller

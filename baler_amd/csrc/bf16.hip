@@ -403,179 +403,78 @@ __global__ void __launch_bounds__(256) pack16_k(const float *__restrict__ params
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) dst[i] = (T)(src[i] >= 0 ? params[src[i]] : 0.f);
 }
-struct Bf16Ops;
-struct Bf16State {
-    const Bf16Ops *ops = nullptr;
-    DevBuf wsrc[2], bsrc[2];     // index maps (encoder half, decoder half)
-    DevBuf w[2], b[2];           // packed bf16 fragments / fp32 bias fragments
-    DevBuf zscratch;             // latent codes between the two launches of forward_loss
-    int wcount[2] = {0, 0}, bcount[2] = {0, 0};
-    int grid = 256;
-};
-struct Bf16Ops {
-    int (*setup)(bamd_handle *, Bf16State *);
-    int (*run)(bamd_handle *, Bf16State *, bool dec, const void *xin, int in_f64, int64_t n, const double *feats, void *out,
-               int out_f64, const uint8_t *imask, const void *xref, int xref_f64, const double *xref_feats, double *loss_part,
-               hipStream_t s);
-    int z_dim, n_features;
-    bool half;                   // the fragments are binary16 (BAMD_MODE_F16), not bfloat16
-};
-Bf16State *bstate(bamd_handle *h) { return (Bf16State *)h->bf16_state; }
-
-template <class V, int F, int Z> struct BImpl {
-    using N = BNet<F, Z>;
-    static bool matches(const bamd_handle *h) {
-        if (h->L != 8) return false;
-        for (int i = 0; i <= 8; ++i)
-            if (h->dims[i] != N::dim(i)) return false;
-        return true;
-    }
-    static int setup(bamd_handle *h, Bf16State *st) {
-        for (int hf = 0; hf < 2; ++hf) {
-            std::vector<int> wsrc, bsrc;
-            fragment_maps<N>(hf, wsrc, bsrc);
-            st->wcount[hf] = (int)wsrc.size();
-            st->bcount[hf] = (int)bsrc.size();
-            int rc = st->wsrc[hf].ensure(wsrc.size() * sizeof(int));
-            if (rc) return rc;
-            rc = st->bsrc[hf].ensure(bsrc.size() * sizeof(int));
-            if (rc) return rc;
-            rc = st->w[hf].ensure(wsrc.size() * sizeof(__bf16));
-            if (rc) return rc;
-            rc = st->b[hf].ensure(bsrc.size() * sizeof(float));
-            if (rc) return rc;
-            BAMD_HIP(hipMemcpy(st->wsrc[hf].p, wsrc.data(), wsrc.size() * sizeof(int), hipMemcpyHostToDevice));
-            BAMD_HIP(hipMemcpy(st->bsrc[hf].p, bsrc.data(), bsrc.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, false, BAMD_F32>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)N::lds_bytes(0)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, false, BAMD_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)N::lds_bytes(0)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, true, BAMD_F32>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)N::lds_bytes(1)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, true, BAMD_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)N::lds_bytes(1)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, true, BAMD_F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)N::lds_bytes(1)));
-        BAMD_HIP(hipFuncSetAttribute((const void *)bf16_infer_kernel<V, F, Z, true, BAMD_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)N::lds_bytes(1)));
-        return BAMD_OK;
-    }
-    static int run(bamd_handle *h, Bf16State *st, bool dec, const void *xin, int in_f64, int64_t n, const double *feats, void *out,
-                   int out_f64, const uint8_t *imask, const void *xref, int xref_f64, const double *xref_feats, double *loss_part,
-                   hipStream_t s) {
-        const int64_t npass = (n + kRowsPerPass - 1) / kRowsPerPass;
-        int64_t wg = (npass + kWaves - 1) / kWaves;
-        const int grid = (int)(wg < 1 ? 1 : (wg > st->grid ? st->grid : wg));
-        auto go = [&](auto decv, auto inv) {      // in_f64 / out_f64 are bamd_dtype codes: 16-bit for the latent side of a decode / an encode
-            constexpr bool D_ = decltype(decv)::value;
-            constexpr int I_ = decltype(inv)::value;
-            hipLaunchKernelGGL((bf16_infer_kernel<V, F, Z, D_, I_>), dim3(grid), dim3(64 * kWaves), N::lds_bytes(D_ ? 1 : 0), s,
-                               (const uint4 *)st->w[D_ ? 1 : 0].p, (const v4 *)st->b[D_ ? 1 : 0].p, xin, n, feats, out, out_f64, imask, xref,
-                               xref_f64, xref_feats, loss_part);
-        };
-        using i32 = std::integral_constant<int, BAMD_F32>;
-        using i64 = std::integral_constant<int, BAMD_F64>;
-        if (dec && in_f64 == BAMD_F16) go(std::true_type(), std::integral_constant<int, BAMD_F16>());
-        else if (dec && in_f64 == BAMD_BF16) go(std::true_type(), std::integral_constant<int, BAMD_BF16>());
-        else if (dec && in_f64) go(std::true_type(), i64());
-        else if (dec) go(std::true_type(), i32());
-        else if (in_f64) go(std::false_type(), i64());
-        else go(std::false_type(), i32());
-        BAMD_HIP(hipGetLastError());
-        return grid;
-    }
-    static const Bf16Ops *ops() {
-        static const Bf16Ops o = {setup, run, Z, F, std::is_same<V, h8>::value};
-        return &o;
+// What Infer16Impl (bf16_net.hpp) asks of this file's kernels, for either element type
+template <class V> struct Policy16 {
+    using T = typename Elem<V>::T;
+    static constexpr int rows_per_pass = kRowsPerPass, waves = kWaves;
+    static constexpr size_t frag_bytes = sizeof(T);
+    template <int F, int Z> static constexpr size_t lds_bytes(int half) { return BNet<F, Z>::lds_bytes(half); }
+    template <int F, int Z, bool DEC, int IN> static constexpr Infer16Kernel kernel() { return bf16_infer_kernel<V, F, Z, DEC, IN>; }
+    static void pack(const float *params, const int *src, int count, void *dst, hipStream_t s) {
+        hipLaunchKernelGGL(pack16_k<T>, dim3((count + 255) / 256), dim3(256), 0, s, params, src, count, (T *)dst);
     }
 };
-
-template <class V> const Bf16Ops *find16(const bamd_handle *h) {
-    if (BImpl<V, 24, 15>::matches(h)) return BImpl<V, 24, 15>::ops();
-    if (BImpl<V, 24, 12>::matches(h)) return BImpl<V, 24, 12>::ops();
-    if (BImpl<V, 24, 8>::matches(h)) return BImpl<V, 24, 8>::ops();
-    if (BImpl<V, 24, 6>::matches(h)) return BImpl<V, 24, 6>::ops();
-    // the other latent sizes of the compression-ratio knob (see fused.hip find_ops)
-    if (BImpl<V, 24, 10>::matches(h)) return BImpl<V, 24, 10>::ops();
-    if (BImpl<V, 24, 5>::matches(h)) return BImpl<V, 24, 5>::ops();
-    if (BImpl<V, 24, 4>::matches(h)) return BImpl<V, 24, 4>::ops();
-    if (BImpl<V, 24, 3>::matches(h)) return BImpl<V, 24, 3>::ops();
-    if (BImpl<V, 24, 2>::matches(h)) return BImpl<V, 24, 2>::ops();
-    return nullptr;
-}
+Infer16State *state16(bamd_handle *h) { return (Infer16State *)h->infer16_state; }
 
 }  // namespace
 
-bool bf16_has_kernels(const bamd_handle *h) { return h->leaky() && find16<bf8>(h) != nullptr; }      // (the same shapes for both types)
+bool bf16_has_kernels(const bamd_handle *h) { return infer16_find<Policy16<bf8>>(h) != nullptr; }      // (the same shapes for both types)
 
-int bf16_setup(bamd_handle *h) {
-    const Bf16Ops *ops = !h->leaky() ? nullptr : h->mode == BAMD_MODE_F16 ? find16<h8>(h) : find16<bf8>(h);
+// ---- the entry points of the three modes: everything mode-specific is behind the state's ops ----
+int infer16_setup(bamd_handle *h) {
+    const Infer16Ops *ops = h->mode == BAMD_MODE_F16X3 ? f16x3_find_ops(h)
+                            : h->mode == BAMD_MODE_F16 ? infer16_find<Policy16<h8>>(h) : infer16_find<Policy16<bf8>>(h);
     if (!ops) {
-        set_error("BAMD_MODE_BF16 / BAMD_MODE_F16 are instantiated for the 24-column AE (latent 15/12/8/6) and the wide models (2500-25, 512-6) only; use BAMD_MODE_F32");
+        set_error("BAMD_MODE_BF16 / BAMD_MODE_F16 / BAMD_MODE_F16X3 are instantiated for the 24-column AE with LeakyReLU (latent "
+                  "15/12/10/8/6/5/4/3/2) only; use BAMD_MODE_F32");
         return BAMD_ERR_UNSUPPORTED;
     }
-    Bf16State *st = new Bf16State();
+    Infer16State *st = new Infer16State();
     st->ops = ops;
-    h->bf16_state = st;
+    h->infer16_state = st;
     return ops->setup(h, st);
 }
 
-void bf16_teardown(bamd_handle *h) {
-    Bf16State *st = bstate(h);
+void infer16_teardown(bamd_handle *h) {
+    Infer16State *st = state16(h);
     if (!st) return;
     for (int i = 0; i < 2; ++i) { st->wsrc[i].release(); st->bsrc[i].release(); st->w[i].release(); st->b[i].release(); }
     st->zscratch.release();
     delete st;
-    h->bf16_state = nullptr;
+    h->infer16_state = nullptr;
 }
 
-int bf16_pack(bamd_handle *h, hipStream_t s) {
-    Bf16State *st = bstate(h);
-    for (int hf = 0; hf < 2; ++hf) {
-        if (st->ops->half)
-            hipLaunchKernelGGL(pack16_k<_Float16>, dim3((st->wcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
-                               (const int *)st->wsrc[hf].p, st->wcount[hf], (_Float16 *)st->w[hf].p);
-        else
-            hipLaunchKernelGGL(pack16_k<__bf16>, dim3((st->wcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
-                               (const int *)st->wsrc[hf].p, st->wcount[hf], (__bf16 *)st->w[hf].p);
-        hipLaunchKernelGGL(pack_bias_k, dim3((st->bcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
-                           (const int *)st->bsrc[hf].p, st->bcount[hf], (float *)st->b[hf].p);
-    }
-    BAMD_HIP(hipGetLastError());
-    return BAMD_OK;
+int infer16_pack(bamd_handle *h, hipStream_t s) { return state16(h)->ops->pack(h, state16(h), s); }
+
+int infer16_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype, hipStream_t s) {
+    Infer16State *st = state16(h);
+    return st->ops->run(h, st, false, x, x_dtype == BAMD_F64, n, features, z, z_dtype, nullptr, nullptr, 0, nullptr, nullptr, s);
 }
 
-int bf16_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype, hipStream_t s) {
-    Bf16State *st = bstate(h);
-    int rc = st->ops->run(h, st, false, x, x_dtype == BAMD_F64, n, features, z, z_dtype, nullptr, nullptr, 0, nullptr,
-                          nullptr, s);
-    return rc < 0 ? rc : BAMD_OK;
+int infer16_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features, const uint8_t *int_mask, void *out,
+                   int out_dtype, hipStream_t s) {
+    Infer16State *st = state16(h);
+    return st->ops->run(h, st, true, z, z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, nullptr, 0, nullptr, nullptr, s);
 }
 
-int bf16_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features, const uint8_t *int_mask, void *out,
-                int out_dtype, hipStream_t s) {
-    Bf16State *st = bstate(h);
-    int rc = st->ops->run(h, st, true, z, z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, nullptr, 0, nullptr,
-                          nullptr, s);
-    return rc < 0 ? rc : BAMD_OK;
-}
-
-int bf16_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *recon, int recon_dtype,
-                      double *loss_sum, hipStream_t s) {
-    Bf16State *st = bstate(h);
+int infer16_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *recon, int recon_dtype,
+                         double *loss_sum, hipStream_t s) {
+    Infer16State *st = state16(h);
     int rc = st->zscratch.ensure((size_t)n * st->ops->z_dim * sizeof(float));
     if (rc) return rc;
     rc = h->lossp.ensure(sizeof(double) * 1024);
     if (rc) return rc;
     rc = st->ops->run(h, st, false, x, x_dtype == BAMD_F64, n, features, st->zscratch.p, 0, nullptr, nullptr, 0, nullptr, nullptr, s);
-    if (rc < 0) return rc;
-    const int grid = st->ops->run(h, st, true, st->zscratch.p, 0, n, nullptr, recon, recon_dtype == BAMD_F64, nullptr, x,
-                                  x_dtype == BAMD_F64, features, (double *)h->lossp.p, s);
-    if (grid < 0) return grid;
-    hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, grid, 1.0 / st->ops->n_features, loss_sum, 0);
-    BAMD_HIP(hipGetLastError());
-    return BAMD_OK;
+    if (rc) return rc;
+    return st->ops->run(h, st, true, st->zscratch.p, 0, n, nullptr, recon, recon_dtype == BAMD_F64, nullptr, x, x_dtype == BAMD_F64,
+                        features, loss_sum, s);
 }
+
+
+namespace {
+void sum_loss(const double *part, int n, double scale, double *dst, hipStream_t s) {      // behind every instantiation: see bf16_net.hpp
+    hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, part, n, scale, dst, 0);
+}
+}  // namespace
 
 }  // namespace bamd

@@ -1,6 +1,8 @@
 // What the 16-bit inference kernels share (bf16.hip: bfloat16 and binary16; f16x3.hip: split binary16): the operand vector types,
-// the BNet geometry of AE(F, Z) on the 16x16x32 MFMA with its fragment index maps, the row loaders, the bias pack kernel, and the
-// store / loss epilogues of the two fp32 outputs (latent, reconstruction) as functions.  Device code in an anonymous namespace: every translation unit has its own copy.
+// the BNet geometry of AE(F, Z) on the 16x16x32 MFMA with its fragment index maps, the row loaders, the bias pack kernel, the
+// store / loss epilogues of the two fp32 outputs (latent, reconstruction) as functions, and -- at the end -- the host side of a mode:
+// its state, and setup / launch / pack written once over a policy that each file defines beside its kernels.
+// Device code and the host templates in an anonymous namespace: every translation unit has its own copy.
 #pragma once
 #include "bamd_internal.hpp"
 
@@ -8,6 +10,29 @@
 #include <vector>
 
 namespace bamd {
+
+// The state of a bf16 / f16 / fp16x3 handle (h->infer16_state) and the calls of its instantiation.  The entry points (bf16.hpp) work
+// through these alone; which policy filled `ops` is decided once, at setup, by h->mode.
+struct Infer16Ops;
+struct Infer16State {
+    const Infer16Ops *ops = nullptr;
+    DevBuf wsrc[2], bsrc[2];     // index maps (encoder half, decoder half)
+    DevBuf w[2], b[2];           // packed 16-bit fragments (fp16x3: [hi | lo]) / fp32 bias fragments
+    DevBuf zscratch;             // latent codes between the two launches of forward_loss
+    int wcount[2] = {0, 0}, bcount[2] = {0, 0};
+    int grid = 256;
+};
+struct Infer16Ops {
+    int (*setup)(bamd_handle *, Infer16State *);
+    // One launch of half `dec`.  in_dtype / out_dtype are bamd_dtype codes: 16-bit for the latent side of a decode / an encode.
+    // loss_sum (decode with xref): per-workgroup partials into h->lossp (the caller has sized it), summed by a second launch.
+    int (*run)(bamd_handle *, Infer16State *, bool dec, const void *xin, int in_dtype, int64_t n, const double *feats, void *out,
+               int out_dtype, const uint8_t *imask, const void *xref, int xref_f64, const double *xref_feats, double *loss_sum,
+               hipStream_t s);
+    int (*pack)(bamd_handle *, Infer16State *, hipStream_t s);      // h->params (fp32) -> both halves' fragments
+    int z_dim;
+};
+
 namespace {
 
 // The 16-bit element type is a template parameter: V = bf8 (bfloat16, BAMD_MODE_BF16) or h8 (IEEE binary16, BAMD_MODE_F16: the
@@ -208,6 +233,111 @@ __global__ void __launch_bounds__(256) pack_bias_k(const float *__restrict__ par
                                                    float *__restrict__ dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) dst[i] = src[i] >= 0 ? params[src[i]] : 0.f;
+}
+
+// ---- the host side of a mode, over a policy P that states what differs between the kernel families: ----
+//   P::rows_per_pass, P::waves                  16 kMB and kWaves of the file's kernels
+//   P::frag_bytes                               bytes of packed fragment per index-map entry
+//   P::lds_bytes<F, Z>(half)                    dynamic LDS of a launch
+//   P::kernel<F, Z, DEC, IN>()                  the kernel (every family has the signature below)
+//   P::pack(params, src, count, dst, s)         launches the weight pack of one half
+using Infer16Kernel = void (*)(const uint4 *wfrags, const v4 *bias, const void *xin, int64_t n, const double *feats, void *out, int out_dtype,
+                               const uint8_t *imask, const void *xref, int xref_f64, const double *xref_feats, double *loss_part);
+
+// *dst = scale * the sum of n partials: one launch of the file's sum_partials_fixed_k<double>.  Each file DEFINES this behind its
+// instantiations: hipcc emits a template kernel where host code first names it, and named from run() below this kernel would leave the
+// end of the file's code object for a place between the inference kernels.  Here the code objects keep the order they had (f16x3.hip's
+// assembly is unchanged to the byte); forward_loss at 64 rows measured + 0.06 .. 0.11 us with the launch in run() and - 0.12 .. + 0.07 us
+// this way, against 20 - 27 us (profiles/r9_infer16_one_host_side.txt)
+void sum_loss(const double *part, int n, double scale, double *dst, hipStream_t s);
+
+template <class P> int pack_halves(bamd_handle *h, Infer16State *st, hipStream_t s) {
+    for (int hf = 0; hf < 2; ++hf) {
+        P::pack((const float *)h->params.p, (const int *)st->wsrc[hf].p, st->wcount[hf], st->w[hf].p, s);
+        hipLaunchKernelGGL(pack_bias_k, dim3((st->bcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
+                           (const int *)st->bsrc[hf].p, st->bcount[hf], (float *)st->b[hf].p);
+    }
+    BAMD_HIP(hipGetLastError());
+    return BAMD_OK;
+}
+template <class P, int F, int Z> struct Infer16Impl {
+    using N = BNet<F, Z>;
+    static bool matches(const bamd_handle *h) {
+        if (h->L != 8) return false;
+        for (int i = 0; i <= 8; ++i)
+            if (h->dims[i] != N::dim(i)) return false;
+        return true;
+    }
+    template <bool D_, int I_> static int allow_lds() {
+        BAMD_HIP(hipFuncSetAttribute((const void *)P::template kernel<F, Z, D_, I_>(), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)P::template lds_bytes<F, Z>(D_ ? 1 : 0)));
+        return BAMD_OK;
+    }
+    static int setup(bamd_handle *h, Infer16State *st) {
+        for (int hf = 0; hf < 2; ++hf) {
+            std::vector<int> wsrc, bsrc;
+            fragment_maps<N>(hf, wsrc, bsrc);
+            st->wcount[hf] = (int)wsrc.size();
+            st->bcount[hf] = (int)bsrc.size();
+            int rc = st->wsrc[hf].ensure(wsrc.size() * sizeof(int));
+            if (rc) return rc;
+            rc = st->bsrc[hf].ensure(bsrc.size() * sizeof(int));
+            if (rc) return rc;
+            rc = st->w[hf].ensure(wsrc.size() * P::frag_bytes);
+            if (rc) return rc;
+            rc = st->b[hf].ensure(bsrc.size() * sizeof(float));
+            if (rc) return rc;
+            BAMD_HIP(hipMemcpy(st->wsrc[hf].p, wsrc.data(), wsrc.size() * sizeof(int), hipMemcpyHostToDevice));
+            BAMD_HIP(hipMemcpy(st->bsrc[hf].p, bsrc.data(), bsrc.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
+        int rc = allow_lds<false, BAMD_F32>();
+        if (!rc) rc = allow_lds<false, BAMD_F64>();
+        if (!rc) rc = allow_lds<true, BAMD_F32>();
+        if (!rc) rc = allow_lds<true, BAMD_F64>();
+        if (!rc) rc = allow_lds<true, BAMD_F16>();
+        if (!rc) rc = allow_lds<true, BAMD_BF16>();
+        return rc;
+    }
+    static int run(bamd_handle *h, Infer16State *st, bool dec, const void *xin, int in_dtype, int64_t n, const double *feats, void *out,
+                   int out_dtype, const uint8_t *imask, const void *xref, int xref_f64, const double *xref_feats, double *loss_sum,
+                   hipStream_t s) {
+        const int64_t npass = (n + P::rows_per_pass - 1) / P::rows_per_pass;
+        int64_t wg = (npass + P::waves - 1) / P::waves;
+        const int grid = (int)(wg < 1 ? 1 : (wg > st->grid ? st->grid : wg));
+        double *loss_part = loss_sum ? (double *)h->lossp.p : nullptr;
+        auto go = [&](auto decv, auto inv) {
+            constexpr bool D_ = decltype(decv)::value;
+            constexpr int I_ = decltype(inv)::value;
+            constexpr Infer16Kernel kernel = P::template kernel<F, Z, D_, I_>();
+            constexpr size_t lds = P::template lds_bytes<F, Z>(D_ ? 1 : 0);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * P::waves), lds, s,
+                               (const uint4 *)st->w[D_ ? 1 : 0].p, (const v4 *)st->b[D_ ? 1 : 0].p, xin, n, feats, out, out_dtype, imask, xref,
+                               xref_f64, xref_feats, loss_part);
+        };
+        using i32 = std::integral_constant<int, BAMD_F32>;
+        using i64 = std::integral_constant<int, BAMD_F64>;
+        if (dec && in_dtype == BAMD_F16) go(std::true_type(), std::integral_constant<int, BAMD_F16>());
+        else if (dec && in_dtype == BAMD_BF16) go(std::true_type(), std::integral_constant<int, BAMD_BF16>());
+        else if (dec && in_dtype) go(std::true_type(), i64());
+        else if (dec) go(std::true_type(), i32());
+        else if (in_dtype) go(std::false_type(), i64());
+        else go(std::false_type(), i32());
+        if (loss_sum) sum_loss(loss_part, grid, 1.0 / F, loss_sum, s);
+        BAMD_HIP(hipGetLastError());
+        return BAMD_OK;
+    }
+    static const Infer16Ops *ops() {
+        static const Infer16Ops o = {setup, run, pack_halves<P>, Z};
+        return &o;
+    }
+};
+// The instantiation of P's kernels for this handle's shape, or null: AE(24, Z) with LeakyReLU at the fused latent sizes
+template <class P> const Infer16Ops *infer16_find(const bamd_handle *h) {
+    if (!h->leaky()) return nullptr;
+#define BAMD_INFER16(Z_) if (Infer16Impl<P, 24, Z_>::matches(h)) return Infer16Impl<P, 24, Z_>::ops();
+    BAMD_AE24_LATENTS(BAMD_INFER16)
+#undef BAMD_INFER16
+    return nullptr;
 }
 
 }  // namespace

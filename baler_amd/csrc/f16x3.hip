@@ -376,171 +376,26 @@ __global__ void __launch_bounds__(256) pack_split_k(const float *__restrict__ pa
     lo[i] = l;
 }
 
-struct X3Ops;
-struct X3State {
-    const X3Ops *ops = nullptr;
-    DevBuf wsrc[2], bsrc[2];     // index maps (encoder half, decoder half)
-    DevBuf w[2], b[2];           // [hi | lo] binary16 fragments / fp32 bias fragments
-    DevBuf zscratch;             // latent codes between the two launches of forward_loss
-    int wcount[2] = {0, 0}, bcount[2] = {0, 0};
-    int grid = 256;
-};
-struct X3Ops {
-    int (*setup)(bamd_handle *, X3State *);
-    int (*run)(bamd_handle *, X3State *, bool dec, const void *xin, int in_dtype, int64_t n, const double *feats, void *out,
-               int out_f64, const uint8_t *imask, const void *xref, int xref_f64, const double *xref_feats, double *loss_part,
-               hipStream_t s);
-    int z_dim, n_features;
-};
-X3State *xstate(bamd_handle *h) { return (X3State *)h->f16x3_state; }
-
-template <int F, int Z> struct XImpl {
-    using N = BNet<F, Z>;
-    using X = XNet<F, Z>;
-    static bool matches(const bamd_handle *h) {
-        if (h->L != 8) return false;
-        for (int i = 0; i <= 8; ++i)
-            if (h->dims[i] != N::dim(i)) return false;
-        return true;
-    }
-    template <bool D_, int I_> static int allow_lds() {
-        BAMD_HIP(hipFuncSetAttribute((const void *)f16x3_infer_kernel<F, Z, D_, I_>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)X::lds_bytes(D_ ? 1 : 0)));
-        return BAMD_OK;
-    }
-    static int setup(bamd_handle *h, X3State *st) {
-        for (int hf = 0; hf < 2; ++hf) {
-            std::vector<int> wsrc, bsrc;
-            fragment_maps<N>(hf, wsrc, bsrc);
-            st->wcount[hf] = (int)wsrc.size();
-            st->bcount[hf] = (int)bsrc.size();
-            int rc = st->wsrc[hf].ensure(wsrc.size() * sizeof(int));
-            if (rc) return rc;
-            rc = st->bsrc[hf].ensure(bsrc.size() * sizeof(int));
-            if (rc) return rc;
-            rc = st->w[hf].ensure(2 * wsrc.size() * sizeof(_Float16));
-            if (rc) return rc;
-            rc = st->b[hf].ensure(bsrc.size() * sizeof(float));
-            if (rc) return rc;
-            BAMD_HIP(hipMemcpy(st->wsrc[hf].p, wsrc.data(), wsrc.size() * sizeof(int), hipMemcpyHostToDevice));
-            BAMD_HIP(hipMemcpy(st->bsrc[hf].p, bsrc.data(), bsrc.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
-        int rc = allow_lds<false, BAMD_F32>();
-        if (!rc) rc = allow_lds<false, BAMD_F64>();
-        if (!rc) rc = allow_lds<true, BAMD_F32>();
-        if (!rc) rc = allow_lds<true, BAMD_F64>();
-        if (!rc) rc = allow_lds<true, BAMD_F16>();
-        if (!rc) rc = allow_lds<true, BAMD_BF16>();
-        return rc;
-    }
-    static int run(bamd_handle *h, X3State *st, bool dec, const void *xin, int in_dtype, int64_t n, const double *feats, void *out,
-                   int out_f64, const uint8_t *imask, const void *xref, int xref_f64, const double *xref_feats, double *loss_part,
-                   hipStream_t s) {
-        const int64_t npass = (n + kRowsPerPass - 1) / kRowsPerPass;
-        int64_t wg = (npass + kWaves - 1) / kWaves;
-        const int grid = (int)(wg < 1 ? 1 : (wg > st->grid ? st->grid : wg));
-        auto go = [&](auto decv, auto inv) {      // in_dtype / out_f64 are bamd_dtype codes: 16-bit for the latent side of a decode / an encode
-            constexpr bool D_ = decltype(decv)::value;
-            constexpr int I_ = decltype(inv)::value;
-            hipLaunchKernelGGL((f16x3_infer_kernel<F, Z, D_, I_>), dim3(grid), dim3(64 * kWaves), X::lds_bytes(D_ ? 1 : 0), s,
-                               (const uint4 *)st->w[D_ ? 1 : 0].p, (const v4 *)st->b[D_ ? 1 : 0].p, xin, n, feats, out, out_f64, imask, xref,
-                               xref_f64, xref_feats, loss_part);
-        };
-        using i32 = std::integral_constant<int, BAMD_F32>;
-        using i64 = std::integral_constant<int, BAMD_F64>;
-        if (dec && in_dtype == BAMD_F16) go(std::true_type(), std::integral_constant<int, BAMD_F16>());
-        else if (dec && in_dtype == BAMD_BF16) go(std::true_type(), std::integral_constant<int, BAMD_BF16>());
-        else if (dec && in_dtype) go(std::true_type(), i64());
-        else if (dec) go(std::true_type(), i32());
-        else if (in_dtype) go(std::false_type(), i64());
-        else go(std::false_type(), i32());
-        BAMD_HIP(hipGetLastError());
-        return grid;
-    }
-    static const X3Ops *ops() {
-        static const X3Ops o = {setup, run, Z, F};
-        return &o;
+// What Infer16Impl (bf16_net.hpp) asks of this file's kernels
+struct PolicyX3 {
+    static constexpr int rows_per_pass = kRowsPerPass, waves = kWaves;
+    static constexpr size_t frag_bytes = 2 * sizeof(_Float16);      // [hi | lo]
+    template <int F, int Z> static constexpr size_t lds_bytes(int half) { return XNet<F, Z>::lds_bytes(half); }
+    template <int F, int Z, bool DEC, int IN> static constexpr Infer16Kernel kernel() { return f16x3_infer_kernel<F, Z, DEC, IN>; }
+    static void pack(const float *params, const int *src, int count, void *dst, hipStream_t s) {
+        hipLaunchKernelGGL(pack_split_k, dim3((count + 255) / 256), dim3(256), 0, s, params, src, count, (_Float16 *)dst, (_Float16 *)dst + count);
     }
 };
-
-const X3Ops *find_x3(const bamd_handle *h) {      // the nine fused latent sizes of the 24-column AE (bf16.hip, find16)
-    if (XImpl<24, 15>::matches(h)) return XImpl<24, 15>::ops();
-    if (XImpl<24, 12>::matches(h)) return XImpl<24, 12>::ops();
-    if (XImpl<24, 10>::matches(h)) return XImpl<24, 10>::ops();
-    if (XImpl<24, 8>::matches(h)) return XImpl<24, 8>::ops();
-    if (XImpl<24, 6>::matches(h)) return XImpl<24, 6>::ops();
-    if (XImpl<24, 5>::matches(h)) return XImpl<24, 5>::ops();
-    if (XImpl<24, 4>::matches(h)) return XImpl<24, 4>::ops();
-    if (XImpl<24, 3>::matches(h)) return XImpl<24, 3>::ops();
-    if (XImpl<24, 2>::matches(h)) return XImpl<24, 2>::ops();
-    return nullptr;
-}
 
 }  // namespace
 
-bool f16x3_has_kernels(const bamd_handle *h) { return h->leaky() && find_x3(h) != nullptr; }
+const Infer16Ops *f16x3_find_ops(const bamd_handle *h) { return infer16_find<PolicyX3>(h); }
 
-int f16x3_setup(bamd_handle *h) {
-    const X3Ops *ops = h->leaky() ? find_x3(h) : nullptr;
-    if (!ops) {
-        set_error("BAMD_MODE_F16X3 is instantiated for the 24-column AE with LeakyReLU (latent 15/12/10/8/6/5/4/3/2) only; use BAMD_MODE_F32");
-        return BAMD_ERR_UNSUPPORTED;
-    }
-    X3State *st = new X3State();
-    st->ops = ops;
-    h->f16x3_state = st;
-    return ops->setup(h, st);
-}
 
-void f16x3_teardown(bamd_handle *h) {
-    X3State *st = xstate(h);
-    if (!st) return;
-    for (int i = 0; i < 2; ++i) { st->wsrc[i].release(); st->bsrc[i].release(); st->w[i].release(); st->b[i].release(); }
-    st->zscratch.release();
-    delete st;
-    h->f16x3_state = nullptr;
+namespace {
+void sum_loss(const double *part, int n, double scale, double *dst, hipStream_t s) {      // behind every instantiation: see bf16_net.hpp
+    hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, part, n, scale, dst, 0);
 }
-
-int f16x3_pack(bamd_handle *h, hipStream_t s) {
-    X3State *st = xstate(h);
-    for (int hf = 0; hf < 2; ++hf) {
-        hipLaunchKernelGGL(pack_split_k, dim3((st->wcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
-                           (const int *)st->wsrc[hf].p, st->wcount[hf], (_Float16 *)st->w[hf].p, (_Float16 *)st->w[hf].p + st->wcount[hf]);
-        hipLaunchKernelGGL(pack_bias_k, dim3((st->bcount[hf] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
-                           (const int *)st->bsrc[hf].p, st->bcount[hf], (float *)st->b[hf].p);
-    }
-    BAMD_HIP(hipGetLastError());
-    return BAMD_OK;
-}
-
-int f16x3_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype, hipStream_t s) {
-    X3State *st = xstate(h);
-    int rc = st->ops->run(h, st, false, x, x_dtype == BAMD_F64, n, features, z, z_dtype, nullptr, nullptr, 0, nullptr, nullptr, s);
-    return rc < 0 ? rc : BAMD_OK;
-}
-
-int f16x3_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features, const uint8_t *int_mask, void *out,
-                 int out_dtype, hipStream_t s) {
-    X3State *st = xstate(h);
-    int rc = st->ops->run(h, st, true, z, z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, nullptr, 0, nullptr, nullptr, s);
-    return rc < 0 ? rc : BAMD_OK;
-}
-
-int f16x3_forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *recon, int recon_dtype,
-                       double *loss_sum, hipStream_t s) {
-    X3State *st = xstate(h);
-    int rc = st->zscratch.ensure((size_t)n * st->ops->z_dim * sizeof(float));
-    if (rc) return rc;
-    rc = h->lossp.ensure(sizeof(double) * 1024);
-    if (rc) return rc;
-    rc = st->ops->run(h, st, false, x, x_dtype == BAMD_F64, n, features, st->zscratch.p, 0, nullptr, nullptr, 0, nullptr, nullptr, s);
-    if (rc < 0) return rc;
-    const int grid = st->ops->run(h, st, true, st->zscratch.p, 0, n, nullptr, recon, recon_dtype == BAMD_F64, nullptr, x,
-                                  x_dtype == BAMD_F64, features, (double *)h->lossp.p, s);
-    if (grid < 0) return grid;
-    hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, grid, 1.0 / st->ops->n_features, loss_sum, 0);
-    BAMD_HIP(hipGetLastError());
-    return BAMD_OK;
-}
+}  // namespace
 
 }  // namespace bamd

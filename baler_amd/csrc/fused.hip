@@ -4589,7 +4589,7 @@ template <int F, int Z> struct ImplWideBf16 {
 // blocks at ratio 100, exafel1_config.py:14-15,33) and the 512-column encoder of BASELINE configs[4].  Anything else runs on
 // generic.hip, and bamd_create says so once (bamd_path_of() = BAMD_PATH_GENERIC).
 #define BAMD_AE24(Z_) if (Impl<24, Z_>::matches(h)) return Impl<24, Z_>::ops();
-#define BAMD_AE24_ALL BAMD_AE24(15) BAMD_AE24(12) BAMD_AE24(10) BAMD_AE24(8) BAMD_AE24(6) BAMD_AE24(5) BAMD_AE24(4) BAMD_AE24(3) BAMD_AE24(2)
+#define BAMD_AE24_ALL BAMD_AE24_LATENTS(BAMD_AE24)
 // BALER_AMD_WIDE_CLASS: 0 = no run-time-width wide class (such shapes run layer by layer); "force" = the class also for the shapes
 // that have an exact instantiation (tests: class vs exact on the same model)
 static bool wide_class_on() { const char *e = getenv("BALER_AMD_WIDE_CLASS"); return !(e && e[0] == '0'); }
