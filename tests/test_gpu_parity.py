@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import grad_tensors as gt
 from baler_amd import native, synth
 from oracle import c_oracle as orc
 
@@ -224,11 +225,7 @@ def test_gradients_golden(golden, data10k, mode, tol):
     assert rel(norms, g["tensor_l2"]) < tol
     # full vector against the oracle on the same inputs, per tensor
     _, go = orc.fwd_bwd(dims, flat, x)
-    off = 0
-    for l in range(8):
-        for n in (dims[l + 1] * dims[l], dims[l + 1]):
-            assert rel(gh[off:off + n], go[off:off + n]) < tol, (l, n)
-            off += n
+    gt.assert_per_tensor(gh[:-1], go, dims, tol, f"golden {mode}")
     # bitwise reproducible run to run (fixed-order reductions)
     grads2 = torch.zeros_like(p)
     h.fwd_bwd(dev(x), grads2)
@@ -267,10 +264,12 @@ def test_fp64_fused_step_ragged(n, data10k):
     lo, go = orc.fwd_bwd(dims, flat, x)
     gh = grads.cpu().numpy()
     assert rel(gh[:-1], go) < TOL64 and abs(gh[-1] - lo) < TOL64 * lo
+    gt.assert_per_tensor(gh[:-1], go, dims, TOL64, f"fp64 n={n}")
     g2 = torch.zeros_like(p)
     h.fwd_bwd(dev(x.astype(np.float32)), g2)                                 # float32 rows are widened on load
     lo32, go32 = orc.fwd_bwd(dims, flat, x.astype(np.float32).astype(np.float64))
     assert rel(g2.cpu().numpy()[:-1], go32) < TOL64
+    gt.assert_per_tensor(g2.cpu().numpy()[:-1], go32, dims, TOL64, f"fp64 n={n} float32 rows")
     # one-call step == two-call step
     m1, v1, m2, v2 = (torch.zeros_like(p) for _ in range(4))
     p1, p2 = p.clone(), p.clone()
@@ -285,6 +284,7 @@ def test_fp64_fused_step_ragged(n, data10k):
     assert torch.equal(g3, g4)
     _, go2 = orc.fwd_bwd(dims, p2.cpu().numpy()[:-1], x)
     assert rel(g4.cpu().numpy()[:-1], go2) < TOL64
+    gt.assert_per_tensor(g4.cpu().numpy()[:-1], go2, dims, TOL64, f"fp64 n={n} after the step")
 
 
 @pytest.mark.parametrize("F,Z", [(30, 8), (25, 10), (47, 12), (63, 15), (16, 4), (1, 1), (33, 15), (24, 16), (40, 20), (63, 31), (31, 17)])
@@ -328,10 +328,12 @@ def test_fp64_any_narrow_table_runs_fused(F, Z):
         h.fwd_bwd(dev(x), grads)
         gh = grads.cpu().numpy()
         assert rel(gh[:-1], go) < TOL64 and abs(gh[-1] - lo) < TOL64 * lo, n
+        gt.assert_per_tensor(gh[:-1], go, dims, TOL64, f"fp64 AE({F}, {Z}) n={n}")
     lo2, go2 = orc.fwd_bwd(dims, flat, xn)
     g2 = torch.zeros_like(p)
     h.fwd_bwd(dev(raw), g2, features=feats)
     assert rel(g2.cpu().numpy()[:-1], go2) < TOL64
+    gt.assert_per_tensor(g2.cpu().numpy()[:-1], go2, dims, TOL64, f"fp64 AE({F}, {Z}) normalise-on-load")
     x = rng.random((512, F))
     m1, v1, m2, v2 = (torch.zeros_like(p) for _ in range(4))
     p1, p2 = p.clone(), p.clone()
@@ -368,6 +370,7 @@ def test_fp64_mid_width_small_batch_step_is_fused(F, Z, monkeypatch, capfd):
         h.fwd_bwd(dev(x), g)
         gh = g.cpu().numpy()
         assert rel(gh[:-1], go) < TOL64 and abs(gh[-1] - lo) < TOL64 * lo, (F, Z, n)
+        gt.assert_per_tensor(gh[:-1], go, dims, TOL64, f"fp64 AE({F}, {Z}) n={n}")
         if n in (37, 512):
             monkeypatch.setenv("BALER_AMD_F64_QCHAIN_BLKS", "0")       # the layer-wise kernels on the same batch
             g2 = torch.zeros_like(p)
@@ -378,6 +381,7 @@ def test_fp64_mid_width_small_batch_step_is_fused(F, Z, monkeypatch, capfd):
             h.fwd_bwd(dev(x.astype(np.float32)), g3)                   # float32 rows are widened on load
             _, go32 = orc.fwd_bwd(dims, flat, x.astype(np.float32).astype(np.float64))
             assert rel(g3.cpu().numpy()[:-1], go32) < TOL64
+            gt.assert_per_tensor(g3.cpu().numpy()[:-1], go32, dims, TOL64, f"fp64 AE({F}, {Z}) n={n} float32 rows")
     # several chunks (ragged last one), gradients added in chunk order; a batch beyond one chunk through train_step (fwd_bwd + the Adam kernel)
     monkeypatch.setenv("BALER_AMD_F64_QCHAIN_BLKS", "300")
     x = rng.random((20001, F))
@@ -385,6 +389,7 @@ def test_fp64_mid_width_small_batch_step_is_fused(F, Z, monkeypatch, capfd):
     g = torch.zeros_like(p)
     h.fwd_bwd(dev(x), g)
     assert rel(g.cpu().numpy()[:-1], go) < TOL64 and abs(g.cpu().numpy()[-1] - lo) < TOL64 * lo
+    gt.assert_per_tensor(g.cpu().numpy()[:-1], go, dims, TOL64, f"fp64 AE({F}, {Z}) n=20001 in chunks")
     pa, ma, va = p.clone(), torch.zeros_like(p), torch.zeros_like(p)
     ha, _ = make_handle(dims, flat, "fp64")
     ha.train_step(dev(x), pa, ma, va, 1, 1e-3)
@@ -418,6 +423,7 @@ def test_fp64_mid_width_small_batch_step_is_fused(F, Z, monkeypatch, capfd):
     h.fwd_bwd(dev(raw), g, features=dev(feats))
     lo, go = orc.fwd_bwd(dims, flat, orc.normalize(raw))
     assert rel(g.cpu().numpy()[:-1], go) < TOL64
+    gt.assert_per_tensor(g.cpu().numpy()[:-1], go, dims, TOL64, f"fp64 AE({F}, {Z}) normalise-on-load")
     # the one-call step == the two-call step, and the next step (and the layer-wise encode) see the new weights
     x = rng.random((512, F))
     g = torch.zeros_like(p)
@@ -435,6 +441,7 @@ def test_fp64_mid_width_small_batch_step_is_fused(F, Z, monkeypatch, capfd):
     pn = p2.cpu().numpy()[:-1]
     _, go2 = orc.fwd_bwd(dims, pn, x)
     assert rel(g4.cpu().numpy()[:-1], go2) < TOL64
+    gt.assert_per_tensor(g4.cpu().numpy()[:-1], go2, dims, TOL64, f"fp64 AE({F}, {Z}) after the step")
     assert rel(h1.encode(dev(x)).cpu().numpy(), orc.encode(dims, pn, x)) < TOL64
 
 
@@ -460,6 +467,7 @@ def test_fp64_register_chain_equals_exchange_chain(n, monkeypatch):
         h.fwd_bwd(dev(raw), g, features=dev(feats))
         got[tag] = g.cpu().numpy()
         assert rel(got[tag][:-1], go) < TOL64 and abs(got[tag][-1] - lo) < TOL64 * max(lo, 1e-300), tag
+        gt.assert_per_tensor(got[tag][:-1], go, dims, TOL64, f"fp64 n={n} {tag}")
     assert np.array_equal(got["registers"][:-1], got["exchange"][:-1])
     assert abs(got["registers"][-1] - got["exchange"][-1]) <= 1e-13 * max(abs(got["exchange"][-1]), 1e-300)
     # the 4-row chain (chain64q_kernel, v_mfma_f64_4x4x4: four rows per workgroup) sums every contraction in two interleaved chains and
@@ -488,6 +496,7 @@ def test_fp64_fused_step_beyond_one_chunk(n, chunk, monkeypatch):
     lo, go = orc.fwd_bwd(dims, flat, x)
     gh = grads.cpu().numpy()
     assert rel(gh[:-1], go) < TOL64 and abs(gh[-1] - lo) < TOL64 * lo
+    gt.assert_per_tensor(gh[:-1], go, dims, TOL64, f"fp64 n={n} chunk={chunk}")
     m1, v1, m2, v2 = (torch.zeros_like(p) for _ in range(4))
     p1, p2 = p.clone(), p.clone()
     h1, _ = make_handle(dims, flat, "fp64")
@@ -591,12 +600,8 @@ def test_cfd_dense_golden(golden):
     assert abs(gh[-1] - g["loss"]) < 1e-4 * abs(g["loss"])
     lo, go = orc.fwd_bwd(dims, flat, x.cpu().numpy().astype(np.float64))
     assert abs(gh[-1] - lo) < TOL32 * lo
-    norms, off = [], 0
-    for l in range(8):
-        for n in (dims[l + 1] * dims[l], dims[l + 1]):
-            norms.append(np.linalg.norm(gh[off:off + n]))
-            assert rel(gh[off:off + n], go[off:off + n]) < TOL32, (l, n)
-            off += n
+    gt.assert_per_tensor(gh[:-1], go, dims, TOL32, "CFD_dense_AE golden")
+    norms = [np.linalg.norm(gh[s]) for _, s in gt.tensor_slices(dims)]
     assert rel(norms, g["grad_tensor_l2"]) < 1e-4
 
 
@@ -948,12 +953,10 @@ def test_any_narrow_table_runs_fused(F, Z):
         h.fwd_bwd(dev(x), grads)
         gh = grads.cpu().numpy().astype(np.float64)
         assert rel(gh[:-1], go) < TOL32 and abs(gh[-1] - lo) < TOL32 * lo, n
-        off = 0
-        for l in range(8):      # per tensor too, up to the reference's batch size (at 20,000 uniform rows single tensors are sums of 20,000
-            for cnt in (dims[l + 1] * dims[l], dims[l + 1]):      # cancelling float32 terms: 1e-5 .. 3e-5 on en1 / en2.weight; the whole vector holds 1e-5)
-                if n <= 513:
-                    assert rel(gh[off:off + cnt], go[off:off + cnt]) < TOL32, (n, l, cnt)
-                off += cnt
+        # per tensor too, up to the reference's batch size (at 20,000 uniform rows single tensors are sums of 20,000 cancelling float32
+        # terms: 1e-5 .. 3e-5 on en1 / en2.weight; the whole vector holds 1e-5)
+        if n <= 513:
+            gt.assert_per_tensor(gh[:-1], go, dims, TOL32, f"AE({F}, {Z}) n={n}")
     lo2, go2 = orc.fwd_bwd(dims, flat, xn)
     g2 = torch.zeros_like(p)
     h.fwd_bwd(dev(raw), g2, features=feats)

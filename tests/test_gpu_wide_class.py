@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import grad_tensors as gt
 from baler_amd import native
 from oracle import c_oracle as orc
 from test_gpu_parity import TOL32, dev, make_handle, off_the_kink, rel
@@ -46,11 +47,7 @@ def _check(dims, flat, h, p, sizes, seed, per_tensor=True):
         gh = g.cpu().numpy().astype(np.float64)
         assert rel(gh[:-1], go) < TOL32 and abs(gh[-1] - lo) < TOL32 * lo, ("fwd_bwd", F, dims[4], n, rel(gh[:-1], go))
         if per_tensor:
-            off = 0
-            for l in range(8):
-                for cnt in (dims[l + 1] * dims[l], dims[l + 1]):
-                    assert rel(gh[off:off + cnt], go[off:off + cnt]) < 2 * TOL32, ("tensor", F, n, l, cnt)
-                    off += cnt
+            gt.assert_per_tensor(gh[:-1], go, dims, 2 * TOL32, f"AE({F}, {dims[4]}) n={n}")
 
 
 @pytest.mark.parametrize("F,Z", [(80, 16), (100, 1), (127, 31), (96, 20)])
