@@ -67,7 +67,7 @@ Family infer_family(const bamd_handle *h) {
     if (h->infer16_state) return h->mode == BAMD_MODE_BF16 ? Family::Bf16 : h->mode == BAMD_MODE_F16 ? Family::F16 : Family::F16X3;
     if (h->fpga_state) return Family::Fpga;
     if (h->fused_ok) return Family::Fused;
-    if (h->mode == BAMD_MODE_F64 && h->fused64_state) return Family::Fused64;
+    if (h->mode == BAMD_MODE_F64 && h->fused64_state) return Family::Fused64;      // (also the wide fp64 class, which only infers)
     return Family::Generic;
 }
 // BF16 handles of the 24-column model train SMALL batches on the fp32 small-batch kernels: measured us per bamd_train_step,
@@ -87,7 +87,7 @@ Family train_family(const bamd_handle *h, int64_t n_rows) {
     if (bf16_kernels_train(h, n_rows)) return Family::Bf16;
     if (fpga_trains(h, n_rows)) return Family::Fpga;
     if (h->fused_ok) return Family::Fused;
-    if (h->mode == BAMD_MODE_F64 && h->fused64_state) return Family::Fused64;
+    if (h->mode == BAMD_MODE_F64 && fused64_trains(h)) return Family::Fused64;      // (the wide fp64 class trains layer by layer)
     return Family::Generic;
 }
 
@@ -215,7 +215,10 @@ int bamd_create_act(const int *dims, int n_layers, int act, int mode, int device
                 : mode == BAMD_MODE_F16X3 ? "BAMD_MODE_F16X3 has kernels for the 24-column AE with LeakyReLU"
                                       : "BAMD_MODE_BF16 has kernels for the 24-column AE and the 2500-25 / 625-7 / 512-6 wide models",
                 path == BAMD_PATH_GENERIC ? "layer-wise kernels" : infer_family(h) == Family::Fpga ? "fused FPGA_prototype_model kernels" : "fused run-time-width kernels");
-    if ((path == BAMD_PATH_GENERIC || path == BAMD_PATH_FUSED_INFER) && !quiet()) {
+    if (path == BAMD_PATH_FUSED_INFER && infer_family(h) == Family::Fused64 && !quiet())
+        fprintf(stderr, "[baler_amd] model %s (fp64) has fused encode / decode / validation kernels only: training runs layer by layer "
+                        "(generic.hip, activations through HBM)\n", dims_string(h).c_str());
+    else if ((path == BAMD_PATH_GENERIC || path == BAMD_PATH_FUSED_INFER) && !quiet()) {
         const std::string infer_only = "throughput training kernels (encode / decode / validation and training steps of up to " +
                                        std::to_string((long long)fused_latency_rows(h)) + " rows are fused)";
         fprintf(stderr, "[baler_amd] model %s (%s) has no fused %s: %s run layer by layer (generic.hip, activations through HBM)\n",
@@ -268,6 +271,7 @@ int bamd_path_of(const bamd_handle *h) {
     case Family::F16: return BAMD_PATH_F16;
     case Family::F16X3: return BAMD_PATH_F16X3;
     case Family::Fused: return fused_trains(h) ? BAMD_PATH_FUSED : BAMD_PATH_FUSED_INFER;
+    case Family::Fused64: return fused64_trains(h) ? BAMD_PATH_FUSED : BAMD_PATH_FUSED_INFER;
     case Family::Generic: return BAMD_PATH_GENERIC;
     default: return BAMD_PATH_FUSED;
     }
@@ -358,6 +362,7 @@ static int infer16_sync(bamd_handle *h, hipStream_t s) { return std::exchange(h-
 // Several families: whichever one trained the batch, the fused family's and the inference family's copies follow.
 static int params_stepped(bamd_handle *h, hipStream_t s) {
     fused_params_changed(h);
+    fused64_params_changed(h);
     if (infer_family(h) == Family::Bf16) {
         if (bf16_train_ok(h)) { h->infer16_stale = true; h->bf16_train_stale = true; }
         else return infer16_pack(h, s);

@@ -40,6 +40,8 @@ int fused64_setup(bamd_handle *h);               // leaves h->fused64_state null
 void fused64_teardown(bamd_handle *h);
 int fused64_pack(bamd_handle *h, hipStream_t s); // h->params (fp64) -> fragment-packed fp64 weights
 void fused64_scatter(bamd_handle *h, const int **sc_off, const int **sc_idx, void **packed);   // for the fused Adam + pack kernel
+bool fused64_trains(const bamd_handle *h);       // false: no fp64 state, or the inference-only wide class (128 .. 4096 columns): training runs on generic.hip
+void fused64_params_changed(bamd_handle *h);     // an optimiser step changed h->params: the wide class re-makes its fragments before its next launch
 // fwd + loss + bwd (hp == nullptr) or the whole training step (hp != nullptr) of a small batch; BAMD_ERR_UNSUPPORTED when this
 // handle / batch size has no such path (the caller then runs the layer-wise kernels)
 // encode / decode / forward + loss; BAMD_ERR_UNSUPPORTED when the shape has no fp64 fused kernels, for a 16-bit latent and for a decode

@@ -22,6 +22,7 @@
 #include <utility>
 
 #include "fused64_net.hpp"
+#include "fused64w.hpp"
 
 namespace bamd {
 namespace {
@@ -734,6 +735,10 @@ struct State64 {
     // BALER_AMD_LATENCY_ROWS (as for fp32) caps the rows the fused pair takes at all: larger batches then run layer by layer.
     int64_t chunk_rows = 262144;
     int64_t max_rows = INT64_MAX;
+    // the wide inference class (Impl64W): no training kernels; `packed` is re-made from h->params by the first inference call after
+    // bamd_load_params or an optimiser step (`stale`), on that call's stream; `wide_cap`: BALER_AMD_F64_WIDE_WGS (0: what the chip holds)
+    bool wide = false, stale = false;
+    int wide_cap = 0;
 };
 struct Ops64 {
     int (*setup)(bamd_handle *, State64 *);
@@ -1026,6 +1031,78 @@ template <int F, int FLO, int Z, int ZLO = 0> struct Impl64Q {
     }
 };
 
+// 128 .. 4096 columns, latent <= 63 (ZLO < z <= ZC), in fp64: encode / decode / forward + loss in one launch each (fused64w.hip); training
+// stays on the layer-wise kernels (step: BAMD_ERR_UNSUPPORTED; train_family in api.hip does not send it here at all).  The packed buffer
+// (fused64w.hpp) is made by pack64_k from a map like build_maps64's; no optimiser kernel scatters into it -- it is re-made lazily.
+// BALER_AMD_F64_WIDE=0 at bamd_create: no such state, the handle runs layer by layer.
+template <int ZC, int ZLO> struct Impl64W {
+    using WL = Wide64<ZC>;
+    using N = typename WL::N;
+    static bool matches(const bamd_handle *h) {
+        if (h->L != 8 || env_off("BALER_AMD_F64_WIDE")) return false;
+        for (int i = 1; i <= 7; ++i)
+            if (i != 4 && h->dims[i] != N::dim(i)) return false;
+        return h->dims[0] == h->dims[8] && h->dims[0] >= kWide64Min && h->dims[0] <= kWide64Max && h->dims[4] > ZLO && h->dims[4] <= ZC;
+    }
+    static int setup(bamd_handle *h, State64 *st) {
+        const int F = h->dims[0], nc = WL::chunks(F);
+        auto dimr = [&](int i) { return h->dims[i]; };
+        auto woff = [&](int l) { return (int)h->w_off[l]; };
+        auto boff = [&](int l) { return (int)h->b_off[l]; };
+        std::vector<int> src(WL::doubles(F), -1);
+        for (int l = 0; l <= 6; ++l) {
+            const int K = N::dim(l), NN = N::dim(l + 1), KT = tiles(K), NT = tiles(NN), Kr = dimr(l), NNr = dimr(l + 1);
+            // forward fragment (q, t) of a narrow layer: lane (i, g) component r = W[16 t + i][16 q + 4 r + g]
+            for (int q = 0; q < KT && l >= 1; ++q)
+                for (int t = 0; t < NT; ++t)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int r = 0; r < 4; ++r) {
+                            const int n = 16 * t + (lane & 15), k = creg_feature(K, q, lane >> 4, r);
+                            if (n < NNr && k >= 0 && k < Kr) src[((size_t)N::wf_off(l) + (q * NT + t) * 64 + lane) * 4 + r] = woff(l) + n * Kr + k;
+                        }
+            // bias fragment (t, g) component r = b[16 t + 4 r + g] (layer 0: what en1's accumulators start from)
+            for (int t = 0; t < NT; ++t)
+                for (int g = 0; g < 4; ++g)
+                    for (int r = 0; r < 4; ++r) {
+                        const int n = creg_feature(NN, t, g, r);
+                        if (n >= 0 && n < NNr) src[((size_t)N::bf_off(l) + t * 4 + g) * 4 + r] = boff(l) + n;
+                    }
+        }
+        for (int c = 0; c < nc; ++c)
+            for (int t = 0; t < kWide64Frags; ++t)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int r = 0; r < 4; ++r) {
+                        const size_t o = (((size_t)c * kWide64Frags + t) * 64 + lane) * 4 + r;
+                        const int i = 16 * t + (lane & 15), j = 16 * c + 4 * r + (lane >> 4);      // en1 (c, t): W_0[i][j]; de4 (c, q = t): W_7[j'][i']
+                        if (i < 200 && j < F) src[WL::en1_off() + o] = woff(0) + i * F + j;
+                        const int n7 = 16 * c + (lane & 15), k7 = 16 * t + 4 * r + (lane >> 4);
+                        if (n7 < F && k7 < 200) src[WL::de4_off(F) + o] = woff(7) + n7 * 200 + k7;
+                    }
+        for (int f = 0; f < F; ++f) src[WL::bias_off(F) + f] = boff(7) + f;
+        st->wide = true;
+        st->stale = true;
+        st->wide_cap = (int)env_ll("BALER_AMD_F64_WIDE_WGS", 0);
+        st->packed_doubles = (int)src.size();
+        int rc = st->pack_src.ensure(src.size() * sizeof(int));
+        if (!rc) rc = st->packed.ensure(src.size() * sizeof(double));
+        if (rc) return rc;
+        BAMD_HIP(hipMemcpy(st->pack_src.p, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice));
+        return fused64w_setup(ZC);
+    }
+    static int step(bamd_handle *, State64 *, const void *, int, int64_t, const double *, double *, const Adam64 *, hipStream_t) {
+        return BAMD_ERR_UNSUPPORTED;      // the caller runs the layer-wise kernels
+    }
+    static int infer(bamd_handle *h, State64 *st, InferKind kind, const void *x, int x_dtype, int64_t n, const double *features, void *out,
+                     int out_dtype, const double *renorm, const uint8_t *imask, double *loss_sum, hipStream_t s) {
+        return fused64w_infer_launch(ZC, h, (const double *)st->packed.p, st->wide_cap, kind, x, x_dtype, n, features, out, out_dtype, renorm, imask,
+                                     loss_sum, s);
+    }
+    static const Ops64 *ops() {
+        static const Ops64 o = {setup, step, infer};
+        return &o;
+    }
+};
+
 const Ops64 *find64(const bamd_handle *h) {
     if (h->mode != BAMD_MODE_F64) return nullptr;
     if (Impl64<24, 15>::matches(h)) return Impl64<24, 15>::ops();
@@ -1055,6 +1132,9 @@ const Ops64 *find64(const bamd_handle *h) {
     if (Impl64Q<95, 79, 63, 31>::matches(h)) return Impl64Q<95, 79, 63, 31>::ops();
     if (Impl64Q<111, 95, 63, 31>::matches(h)) return Impl64Q<111, 95, 63, 31>::ops();
     if (Impl64Q<127, 111, 63, 31>::matches(h)) return Impl64Q<127, 111, 63, 31>::ops();
+    // 128 .. 4096 columns: inference only (Impl64W)
+    if (Impl64W<31, 0>::matches(h)) return Impl64W<31, 0>::ops();
+    if (Impl64W<63, 31>::matches(h)) return Impl64W<63, 31>::ops();
     return nullptr;
 }
 
@@ -1082,18 +1162,33 @@ void fused64_teardown(bamd_handle *h) {
     h->fused64_state = nullptr;
 }
 
-int fused64_pack(bamd_handle *h, hipStream_t s) {
-    State64 *st = st64(h);
-    if (!st) return BAMD_OK;
+static int pack64_now(bamd_handle *h, State64 *st, hipStream_t s) {
     hipLaunchKernelGGL(pack64_k, dim3((st->packed_doubles + 255) / 256), dim3(256), 0, s, (const double *)h->params.p,
                        (const int *)st->pack_src.p, st->packed_doubles, (double *)st->packed.p);
     BAMD_HIP(hipGetLastError());
     return BAMD_OK;
 }
 
+int fused64_pack(bamd_handle *h, hipStream_t s) {
+    State64 *st = st64(h);
+    if (!st) return BAMD_OK;
+    if (st->wide) { st->stale = true; return BAMD_OK; }      // re-made by the next inference call, on its stream
+    return pack64_now(h, st, s);
+}
+
+bool fused64_trains(const bamd_handle *h) {
+    const State64 *st = (const State64 *)h->fused64_state;
+    return st && !st->wide;
+}
+
+void fused64_params_changed(bamd_handle *h) {
+    State64 *st = st64(h);
+    if (st && st->wide) st->stale = true;
+}
+
 void fused64_scatter(bamd_handle *h, const int **sc_off, const int **sc_idx, void **packed) {
     State64 *st = st64(h);
-    if (!st) return;
+    if (!st || st->wide) return;      // (the wide inference class has no scatter lists: its copy is re-made lazily)
     *sc_off = (const int *)st->sc_off.p;
     *sc_idx = (const int *)st->sc_idx.p;
     *packed = st->packed.p;
@@ -1104,7 +1199,7 @@ void fused64_scatter(bamd_handle *h, const int **sc_off, const int **sc_idx, voi
 int fused64_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *grads, void *params, void *m,
                  void *v, const bamd_adam *hp, double *loss_accum, hipStream_t s) {
     State64 *st = st64(h);
-    if (!st || n > st->max_rows || n <= 0) return BAMD_ERR_UNSUPPORTED;
+    if (!st || st->wide || n > st->max_rows || n <= 0) return BAMD_ERR_UNSUPPORTED;
     if (!hp) return st->ops->step(h, st, x, x_dtype, n, features, (double *)grads, nullptr, s);
     Adam64 ad;
     ad.params = (double *)params; ad.pcopy = (double *)h->params.p; ad.m = (double *)m; ad.v = (double *)v;
@@ -1125,6 +1220,8 @@ int fused64_infer(bamd_handle *h, InferKind kind, const void *x, int x_dtype, in
     if (!st || !on || n <= 0) return BAMD_ERR_UNSUPPORTED;
     // the kernels load and store float32 / float64 latents, and un-normalise into float64 only (as renormalize_k)
     if (kind == K_ENCODE ? !dtype_wide(out_dtype) : kind == K_DECODE && (!dtype_wide(x_dtype) || (renorm && out_dtype != BAMD_F64))) return BAMD_ERR_UNSUPPORTED;
+    if (st->wide && std::exchange(st->stale, false))
+        if (const int rc = pack64_now(h, st, s)) return rc;
     return st->ops->infer(h, st, kind, x, x_dtype, n, features, out, out_dtype, renorm, int_mask, loss_sum, s);
 }
 

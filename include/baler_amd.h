@@ -239,7 +239,11 @@ int bamd_create_pjconv(int z_dim, int mode, int device, bamd_handle **out);
  *   - 48 .. 4096 columns, latent <= 63, that no class above takes: the wide-layer kernels with the column count and the latent as
  *     kernel arguments -- encode / decode / forward + loss fused, a training pass = two fused row-local launches + the layer-wise
  *     weight-gradient kernels, as for the exact wide shapes (BAMD_PATH_FUSED; BALER_AMD_WIDE_CLASS=0 switches the class off);
- *   - F64 handles: class instantiations of the fp64 kernels for up to 63 columns with a latent of up to 31;
+ *   - F64 handles: class instantiations of the fp64 kernels for up to 63 columns with a latent of up to 31 (every kernel), up to 127
+ *     columns with a latent of up to 63 (inference, and training steps on the 4-row chain), and 128 .. 4096 columns with a latent of up
+ *     to 63 for encode / decode / forward + loss only (fused64w.hip, the column count and the latent as kernel arguments): such a
+ *     handle trains layer by layer and reports BAMD_PATH_FUSED_INFER; bamd_create says so once on stderr unless BALER_AMD_QUIET=1.
+ *     BALER_AMD_F64_WIDE=0 at bamd_create puts it back on the layer-wise kernels (BAMD_PATH_GENERIC), BALER_AMD_F64_WIDE_WGS caps its grid;
  *   - BAMD_ACT_RELU handles of FPGA_prototype_model (n_features, 20, 10, z, 10, 20, n_features) for n_features <= 64 and z <= 32,
  *     BAMD_MODE_F32 and BAMD_MODE_F64: fused kernels with n_features and z as kernel arguments (fpga.hip; BAMD_PATH_FUSED;
  *     fp32 training batches above 8192 rows run on the layer-wise kernels, which are faster there).
@@ -252,7 +256,8 @@ typedef enum bamd_path {
     BAMD_PATH_FUSED = 1,     /* fused.hip: register chain (24-column AE) or streamed wide layers + chain */
     BAMD_PATH_BF16 = 2,      /* bf16.hip / bf16_train.hip (24-column AE, BAMD_MODE_BF16); its small batches use the fused fp32 step */
     BAMD_PATH_FUSED_INFER = 3, /* 64..127 columns with BALER_AMD_MID_HYBRID=0 or BALER_AMD_WIDE_CLASS=0: fused.hip for encode / decode / forward + loss and
-                              * the small-batch training kernels (larger batches chunk after chunk on the same kernels) */
+                              * the small-batch training kernels (larger batches chunk after chunk on the same kernels); an F64 handle of
+                              * 128 .. 4096 columns: fused64w.hip for encode / decode / forward + loss, training layer by layer */
     BAMD_PATH_F16 = 4,       /* bf16.hip's binary16 instantiations for inference (24-column AE, BAMD_MODE_F16); training on the fused fp32 kernels */
     BAMD_PATH_F16X3 = 5      /* f16x3.hip: split-binary16 inference at fp32 accuracy (24-column AE, BAMD_MODE_F16X3); training on the fused fp32 kernels */
 } bamd_path;
