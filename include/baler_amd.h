@@ -18,7 +18,11 @@
  *  - every pointer argument needs the alignment of its element type and nothing more (a row block of a larger allocation
  *    is a valid argument), and a call reads and writes nothing outside the rows, codes and parameters it was given;
  *  - all work is enqueued asynchronously on the hipStream_t passed as `stream` (void*; NULL =
- *    the default stream); nothing synchronises the host;
+ *    the default stream); nothing synchronises the host, with ONE exception: a call that has to make or grow device memory of the
+ *    library's own -- the create calls (no stream: they allocate and fill their index maps with blocking copies), the first call
+ *    that needs a workspace of the handle, the first handle-free call on a stream (scratch is per device and stream), and a call with
+ *    more rows than any before it -- allocates, and freeing the smaller buffer waits for the device; a repeated call of a size already
+ *    seen never waits (tests/test_gpu_streams.py holds stream order and the absence of a host wait for such calls);
  *  - one handle per (model, device); a handle is not thread-safe, and it is SINGLE-STREAM: the library re-packs its
  *    weight fragments lazily, on the stream of the first call that needs them after an optimiser step, so calls on one
  *    handle must be issued on one stream (or the caller orders its streams with events around every call);

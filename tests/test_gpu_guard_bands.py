@@ -314,8 +314,9 @@ SERVES_RENORM_F32 = {("ae24-fp32", "default"), ("class40-fp32", "default"), ("cl
                      ("ae24z8-bf16", "default")}
 
 
-def family(name, route, monkeypatch):
-    kind, F, Z, mode, env, _, _ = FAMILIES[name]
+def family(name, route, monkeypatch, spec=None):
+    """spec: the FAMILIES entry of a family that another module defines (tests/test_gpu_streams.py)."""
+    kind, F, Z, mode, env, _, _ = spec or FAMILIES[name]
     monkeypatch.setenv("BALER_AMD_QUIET", "1")
     for k, v in {**env, **ROUTES[route]}.items():
         monkeypatch.setenv(k, v)
@@ -336,7 +337,8 @@ def family(name, route, monkeypatch):
     flat = dev(np.concatenate([flat, [0.0]]), pdt)
     ref.flat = host(flat)[:-1]                     # the parameters as the handle holds them (float32 handles: rounded)
     h.load_params(flat)
-    cmode = {native.MODE_F32: "fp32", native.MODE_F64: "fp64", native.MODE_BF16: "bf16"}[h.compute_mode]
+    cmode = {native.MODE_F32: "fp32", native.MODE_F64: "fp64", native.MODE_BF16: "bf16", native.MODE_F16: "fp16",
+             native.MODE_F16X3: "fp16x3"}[h.compute_mode]
     wide = h.dims[0] > 127 and kind == "dense"
     print(f"\n[guard bands] family={name} path={h.path} compute={cmode} routing={route} {ROUTES[route]} env={env}")
     return h, ref, flat, cmode, wide
