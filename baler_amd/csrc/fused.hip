@@ -2620,18 +2620,21 @@ template <class N> constexpr int img_a_rows() {     // 240 up to 31 columns, 256
 // ROLES = true, the ROLE-SPLIT pair (train_dec_roles_kernel / train_enc_roles_kernel, 512 threads): waves 0..3 are CHAIN waves (rows,
 // forward, loss, image writes, the dX chain: the activation stash and the d arrays, no accumulators) and waves 4..7 WEIGHT-GRADIENT
 // waves (dw_phase / dw_flush only: the accumulators and two fragment buffers), so that each SIMD has a second wave to issue from.
-// Same images, same A/B alternation, one barrier per layer across the eight waves: after barrier k the weight-gradient waves read
-// layer l's images while the chain waves write layer l - 1's into the other buffer, which was last read one barrier earlier.  The
-// number of layers per iteration is even in both kernels, so the alternation runs on across iterations and the last dw_phase of a row
-// group runs beside the forward of the next one.  Both roles execute the same barriers: one per layer and iteration, then those of
-// the loss tree.  Tiles are dealt by (wave - 4) exactly as the one-wave pair deals them by wave, every tile sums the same rows in the
-// same order and the loss tree runs over the same 256 chain lanes: the two pairs are bit-identical.
-// The layouts differ in five places, marked (1)..(5) in the two bodies below, and nowhere else:
+// Same images, same A/B alternation, one barrier per layer across the eight waves.  Layer l's barrier sits between the chain waves'
+// image writes of layer l and their dX chain of layer l: behind it the weight-gradient waves read layer l's images (dW(l)) while the
+// chain waves run dX(l) -- the same number of MFMAs by nature -- and then write layer l - 1's images into the other buffer, which
+// was last read one barrier earlier.  The number of layers per iteration is even in both kernels, so the alternation runs on across
+// iterations and the last dw_phase of a row group runs beside the forward of the next one.  Both roles execute the same barriers:
+// ROLE_SYNC(0 .. NB - 1) per iteration, then those of the loss tree.  Tiles are dealt by (wave - 4) exactly as the one-wave pair deals
+// them by wave, every tile sums the same rows in the same order and the loss tree runs over the same 256 chain lanes: the two pairs
+// are bit-identical.
+// The layouts differ in six places, marked (1)..(6) in the two bodies below, and nowhere else:
 //   (1) who runs dw_phase: every wave after each barrier, or waves 4..7 in a loop of their own;
-//   (2) layer 7's slope: from the registers of a7, or from its image (bwd_stage);
-//   (3) where load_rows_finish of the next group's rows sits;
+//   (2) layer 7's slope: from the registers of a7, or from its image (bwd_chain), read back behind the barrier while waves 4..7 read it too;
+//   (3) where the next group's rows (and, in the second kernel, its dZ_1 record) are requested and where load_rows_finish sits;
 //   (4) which waves own the accumulators and flush them;
-//   (5) the loss tree's barriers span four waves or eight (the same text: block_sum_tree sums threads 0..255 either way).
+//   (5) the loss tree's barriers span four waves or eight (the same text: block_sum_tree sums threads 0..255 either way);
+//   (6) the layer's barrier: behind the dX chain (its dW tiles follow in the same wave), or in front of it (dW(l) beside dX(l)).
 
 // the [X_l | dZ_l] image of layer l: X^T with the ones row, then dZ^T
 template <class N, int l>
@@ -2646,11 +2649,11 @@ __device__ __forceinline__ void dw_stage(float *imgA, float *imgB, v4 (&acc)[DW<
     float *img = img_in_a(l) ? imgA : imgB;
     dw_phase<N, l>(img + DW<N, l>::rows_x * kQS, img, acc, lane, wave);
 }
-// backward stage of layer l >= 1 on the chain side: image writes -> dX chain (registers only) -> slope of the activation in front of it
+// backward stage of layer l >= 1 on the chain side, behind its image writes: dX chain (registers only) -> slope of the activation in
+// front of it
 template <class N, class S, int l, bool ROLES>
-__device__ __forceinline__ void bwd_stage(float *imgA, float *imgB, const v4 (&x)[tiles(N::dim(l))], const v4 (&dz)[tiles(N::dim(l + 1))],
+__device__ __forceinline__ void bwd_chain(float *imgA, float *imgB, const v4 (&x)[tiles(N::dim(l))], const v4 (&dz)[tiles(N::dim(l + 1))],
                                           v4 (&dx)[tiles(N::dim(l))], Ring &ring, const WStream &ws, int lane, int wave) {
-    img_write<N, l>(imgA, imgB, x, dz, lane, wave);
     bwd_layer<N, S, l>(dz, dx, ring, ws);
     if constexpr (ROLES && l == 7)          // (2) a7 is dead from its image write on: keeps the chain role inside 256 registers
         lrelu_bwd_img<N::dim(l)>(dx, img_in_a(l) ? imgA : imgB, lane, wave);
@@ -2658,12 +2661,34 @@ __device__ __forceinline__ void bwd_stage(float *imgA, float *imgB, const v4 (&x
         lrelu_bwd(dx, x);
 }
 
+#ifdef BAMD_ROLES_TRACE   // debug build: shader-clock stamps of one workgroup of the training pair at every barrier (tools/roles_trace.py)
+// [kernel: dec, enc][role: wave 0 (chain), wave 4 (weight-gradient)][iteration kRolesTraceIter, + 1][stamp]; stamp 0 / 1 = start / end
+// of the forward, 2 + 2k / 3 + 2k = arrival at / release from the iteration's k-th barrier.  The stores cost the recorded
+// wave a few vector registers: read the trace build's register report before trusting a table (tools/roles_trace.py).
+__device__ unsigned long long g_roles_trace[2][2][2][16];
+constexpr unsigned kRolesTraceWG = 100, kRolesTraceIter = 30;   // the middle of the 61 iterations of a 1M-row call
+__device__ __forceinline__ int roles_trace_slot(int kernel, int64_t grp) {   // wave-uniform: first stamp's index, or -1
+    const unsigned it = (unsigned)(grp - blockIdx.x) / gridDim.x - kRolesTraceIter;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    return blockIdx.x == kRolesTraceWG && (w & 3) == 0 && it < 2 ? ((kernel * 2 + (w >> 2)) * 2 + (int)it) * 16 : -1;
+}
+#define ROLES_T_GROUP(kernel, grp) const int roles_t = roles_trace_slot(kernel, grp)
+#define ROLES_T(i) do { if (roles_t >= 0 && (threadIdx.x & 63) == 0) (&g_roles_trace[0][0][0][0])[roles_t + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define ROLES_T_GROUP(kernel, grp) do {} while (0)
+#define ROLES_T(i) do {} while (0)
+#endif
+// the k-th of the NB barriers of an iteration of the training pair's persistent loop.  Every role's loop runs k = 0 .. NB - 1 once, in
+// order, with the kernel's one NB: a role that ran one barrier less would hang the workgroup.
+#define ROLE_SYNC(k, NB) do { static_assert(0 <= (k) && (k) < (NB), "barrier ordinal"); ROLES_T(2 + 2 * (k)); __syncthreads(); ROLES_T(3 + 2 * (k)); } while (0)
+
 // Decoder-gradient kernel: the whole forward, the loss, the backward chain of layers 7..2; hands dZ_1 to the encoder-gradient kernel.
 template <int F, int Z, bool RT, bool ROLES>
 __device__ __forceinline__ void train_dec_body(const v4 *packed, const void *xin, int in_f64, int64_t n, const double *feats, v4 *slabs,
                                                v4 *dz_out, int fr) {
     using N = Net<F, Z>;
     using S = StreamTrainDec<N>;
+    constexpr int NB = 6;   // barriers per iteration: one per layer 7..2
     // LDS: image buffer A, image buffer B, then the bias fragments where they fit.  (The carve-up stands in both bodies, not in a helper
     // that hands the three pointers back: through a helper hipcc merged 4 .. 36 of dw_phase's fragment reads per kernel, and the class
     // instantiations that spill paid up to 16 B of scratch per lane more -- profiles/r8_f32_train_pair_one_text.txt.)
@@ -2691,17 +2716,18 @@ __device__ __forceinline__ void train_dec_body(const v4 *packed, const void *xin
         int tw = wave - 4;
         for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
             asm volatile("" : "+s"(tw), "+v"(lane));   // see the chain loop
-            __syncthreads();
+            ROLES_T_GROUP(0, grp);
+            ROLE_SYNC(0, NB);
             dw_stage<N, 7>(imgA, imgB, g7, lane, tw);
-            __syncthreads();
+            ROLE_SYNC(1, NB);
             dw_stage<N, 6>(imgA, imgB, g6, lane, tw);
-            __syncthreads();
+            ROLE_SYNC(2, NB);
             dw_stage<N, 5>(imgA, imgB, g5, lane, tw);
-            __syncthreads();
+            ROLE_SYNC(3, NB);
             dw_stage<N, 4>(imgA, imgB, g4, lane, tw);
-            __syncthreads();
+            ROLE_SYNC(4, NB);
             dw_stage<N, 3>(imgA, imgB, g3, lane, tw);
-            __syncthreads();
+            ROLE_SYNC(5, NB);
             dw_stage<N, 2>(imgA, imgB, g2, lane, tw);
         }
         dw_flush<N, 7>(slab, g7, lane, tw); dw_flush<N, 6>(slab, g6, lane, tw); dw_flush<N, 5>(slab, g5, lane, tw);
@@ -2725,6 +2751,8 @@ __device__ __forceinline__ void train_dec_body(const v4 *packed, const void *xin
             const bool valid_next = row_next < n;
             RawRows<F> xraw;
             v4 a2[7], a3[4], a4[tiles(Z)], a5[4], a6[7], a7[13], d8[tiles(F)];
+            ROLES_T_GROUP(0, grp);
+            ROLES_T(0);
             {
                 v4 a0[tiles(F)], a1[13];
 #pragma unroll
@@ -2748,39 +2776,53 @@ __device__ __forceinline__ void train_dec_body(const v4 *packed, const void *xin
                         d8[t][r] = live ? d * (2.0f / (float)(RT ? fr : F)) : 0.f;
                     }
             }
-            // decoder backward: per layer, image writes -> dX chain -> slope -> barrier -> (1) dW tiles, here or in waves 4..7
+            ROLES_T(1);
+            // decoder backward, one-wave pair: per layer, image writes -> dX chain -> slope -> barrier -> (1) dW tiles.
+            // (6) role-split pair: image writes -> barrier -> dX chain -> slope, so that dW(l) of waves 4..7 runs beside dX(l)
             v4 d7[13], d6[7], d5[4], d4[tiles(Z)], d3[4], d2[7];
-            bwd_stage<N, S, 7, ROLES>(imgA, imgB, a7, d8, d7, ring, ws, lane, wave);
-            __syncthreads();
+            img_write<N, 7>(imgA, imgB, a7, d8, lane, wave);
+            if constexpr (ROLES) ROLE_SYNC(0, NB);
+            bwd_chain<N, S, 7, ROLES>(imgA, imgB, a7, d8, d7, ring, ws, lane, wave);
+            if constexpr (!ROLES) ROLE_SYNC(0, NB);
             if constexpr (!ROLES) dw_stage<N, 7>(imgA, imgB, g7, lane, wave);
 
-            bwd_stage<N, S, 6, ROLES>(imgA, imgB, a6, d7, d6, ring, ws, lane, wave);
-            __syncthreads();
+            img_write<N, 6>(imgA, imgB, a6, d7, lane, wave);
+            if constexpr (ROLES) ROLE_SYNC(1, NB);
+            bwd_chain<N, S, 6, ROLES>(imgA, imgB, a6, d7, d6, ring, ws, lane, wave);
+            if constexpr (!ROLES) ROLE_SYNC(1, NB);
             load_rows_issue<F, RT>(xraw, xin, in_f64, row_next, valid_next, lane, fr);   // behind the register peak
             if constexpr (!ROLES) {
                 dw_stage<N, 6>(imgA, imgB, g6, lane, wave);
                 load_rows_finish<F, RT>(a0n, xraw, valid_next, lane, feats, fr);          // (3) landed during the longest dW phase
             }
 
-            bwd_stage<N, S, 5, ROLES>(imgA, imgB, a5, d6, d5, ring, ws, lane, wave);
-            __syncthreads();
-            if constexpr (ROLES) load_rows_finish<F, RT>(a0n, xraw, valid_next, lane, feats, fr);   // (3) landed during layer 5
-            else dw_stage<N, 5>(imgA, imgB, g5, lane, wave);
+            img_write<N, 5>(imgA, imgB, a5, d6, lane, wave);
+            if constexpr (ROLES) ROLE_SYNC(2, NB);
+            bwd_chain<N, S, 5, ROLES>(imgA, imgB, a5, d6, d5, ring, ws, lane, wave);
+            if constexpr (!ROLES) ROLE_SYNC(2, NB);
+            if constexpr (!ROLES) dw_stage<N, 5>(imgA, imgB, g5, lane, wave);
 
-            bwd_stage<N, S, 4, ROLES>(imgA, imgB, a4, d5, d4, ring, ws, lane, wave);
-            __syncthreads();
+            img_write<N, 4>(imgA, imgB, a4, d5, lane, wave);
+            if constexpr (ROLES) ROLE_SYNC(3, NB);
+            bwd_chain<N, S, 4, ROLES>(imgA, imgB, a4, d5, d4, ring, ws, lane, wave);
+            if constexpr (!ROLES) ROLE_SYNC(3, NB);
+            if constexpr (ROLES) load_rows_finish<F, RT>(a0n, xraw, valid_next, lane, feats, fr);   // (3) landed during dX(5) and dX(4)
             if constexpr (!ROLES) dw_stage<N, 4>(imgA, imgB, g4, lane, wave);
 
-            bwd_stage<N, S, 3, ROLES>(imgA, imgB, a3, d4, d3, ring, ws, lane, wave);
-            __syncthreads();
+            img_write<N, 3>(imgA, imgB, a3, d4, lane, wave);
+            if constexpr (ROLES) ROLE_SYNC(4, NB);
+            bwd_chain<N, S, 3, ROLES>(imgA, imgB, a3, d4, d3, ring, ws, lane, wave);
+            if constexpr (!ROLES) ROLE_SYNC(4, NB);
             if constexpr (!ROLES) dw_stage<N, 3>(imgA, imgB, g3, lane, wave);
 
-            bwd_stage<N, S, 2, ROLES>(imgA, imgB, a2, d3, d2, ring, ws, lane, wave);
+            img_write<N, 2>(imgA, imgB, a2, d3, lane, wave);
+            if constexpr (ROLES) ROLE_SYNC(5, NB);
+            bwd_chain<N, S, 2, ROLES>(imgA, imgB, a2, d3, d2, ring, ws, lane, wave);
             // dZ_1 hand-off, [16-row tile][t][lane]: 1 KiB contiguous per store.  Rows beyond n store exact zeros (their dL/drecon
             // was zeroed above), so the second kernel loads the record without a validity select.
 #pragma unroll
             for (int t = 0; t < 7; ++t) dz_out[((row >> 4) * 7 + t) * 64 + lane] = d2[t];
-            __syncthreads();
+            if constexpr (!ROLES) ROLE_SYNC(5, NB);
             if constexpr (!ROLES) dw_stage<N, 2>(imgA, imgB, g2, lane, wave);
             ring_tail<S::total>(ring, ws);
         }
@@ -2802,6 +2844,7 @@ __device__ __forceinline__ void train_enc_body(const v4 *packed, const void *xin
                                                const v4 *dz_in, int fr) {
     using N = Net<F, Z>;
     using S = StreamTrainEnc<N>;
+    constexpr int NB = 2;   // barriers per iteration: one per layer 1..0
     // LDS as in train_dec_body
     constexpr int kImgA = img_a_rows<N>();
     static_assert(img_fits<N, 7>() && img_fits<N, 6>() && img_fits<N, 5>() && img_fits<N, 4>() && img_fits<N, 3>() && img_fits<N, 2>() &&
@@ -2823,9 +2866,10 @@ __device__ __forceinline__ void train_enc_body(const v4 *packed, const void *xin
         int tw = wave - 4;                          // (1) the weight-gradient waves
         for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
             asm volatile("" : "+s"(tw), "+v"(lane));   // see train_dec_body
-            __syncthreads();
+            ROLES_T_GROUP(1, grp);
+            ROLE_SYNC(0, NB);
             dw_stage<N, 1>(imgA, imgB, g1, lane, tw);
-            __syncthreads();
+            ROLE_SYNC(1, NB);
             dw_stage<N, 0>(imgA, imgB, g0, lane, tw);
         }
         dw_flush<N, 1>(slab, g1, lane, tw); dw_flush<N, 0>(slab, g0, lane, tw);
@@ -2851,20 +2895,32 @@ __device__ __forceinline__ void train_enc_body(const v4 *packed, const void *xin
             for (int t = 0; t < tiles(F); ++t) a0[t] = a0n[t];
 #pragma unroll
             for (int t = 0; t < 7; ++t) d2[t] = d2n[t];
+            ROLES_T_GROUP(1, grp);
+            ROLES_T(0);
             fwd_layer<N, S, 0>(a0, a1, ring, ws, bias_lds, lane);
+            ROLES_T(1);
 
-            bwd_stage<N, S, 1, ROLES>(imgA, imgB, a1, d2, d1, ring, ws, lane, wave);
-            __syncthreads();
-            load_rows_issue<F, RT>(xraw, xin, in_f64, row_next, valid_next, lane, fr);   // lands during the long dW phase (ROLES: while it holds the next barrier)
+            img_write<N, 1>(imgA, imgB, a1, d2, lane, wave);
+            if constexpr (ROLES) {                                                        // (6) dW(1) runs beside dX(1)
+                ROLE_SYNC(0, NB);
+                load_rows_issue<F, RT>(xraw, xin, in_f64, row_next, valid_next, lane, fr);   // both requests land during dX(1)
 #pragma unroll
-            for (int t = 0; t < 7; ++t) d2n[t] = dz_in[((row_next >> 4) * 7 + t) * 64 + lane];   // one round past the end stays inside the buffer
+                for (int t = 0; t < 7; ++t) d2n[t] = dz_in[((row_next >> 4) * 7 + t) * 64 + lane];
+            }
+            bwd_chain<N, S, 1, ROLES>(imgA, imgB, a1, d2, d1, ring, ws, lane, wave);
+            if constexpr (!ROLES) {
+                ROLE_SYNC(0, NB);
+                load_rows_issue<F, RT>(xraw, xin, in_f64, row_next, valid_next, lane, fr);   // lands during the long dW phase
+#pragma unroll
+                for (int t = 0; t < 7; ++t) d2n[t] = dz_in[((row_next >> 4) * 7 + t) * 64 + lane];   // one round past the end stays inside the buffer
+            }
             if constexpr (!ROLES) {
                 dw_stage<N, 1>(imgA, imgB, g1, lane, wave);
                 load_rows_finish<F, RT>(a0n, xraw, valid_next, lane, feats, fr);          // (3)
             }
 
             img_write<N, 0>(imgA, imgB, a0, d1, lane, wave);
-            __syncthreads();
+            ROLE_SYNC(1, NB);
             if constexpr (ROLES) load_rows_finish<F, RT>(a0n, xraw, valid_next, lane, feats, fr);   // (3)
             else dw_stage<N, 0>(imgA, imgB, g0, lane, wave);
             ring_tail<S::total>(ring, ws);
@@ -3858,7 +3914,7 @@ static int infer_grid(int64_t n) {
 }
 
 // which training pair fwd_bwd launches where an instantiation has both (BALER_AMD_TRAIN_ROLES overrides it per call): the role-split
-// pair, 1.7 % ahead at 1M rows
+// pair, 3.0 % ahead at 1M rows (1.7 % from the second wave per SIMD, 1.3 % from pairing dW(l) with dX(l))
 constexpr int kTrainRolesDefault = 1;
 
 // RT = true: the instantiation serves a CLASS of narrow tables -- every AE(f, z) with f <= F, z <= Z and the
@@ -4889,6 +4945,12 @@ int fused_train_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, cons
     }
     return train_step_on(h, x, x_dtype, n, features, grads, params, m, v, hp, loss_accum, s);
 }
+
+#ifdef BAMD_ROLES_TRACE
+extern "C" int bamd_debug_roles_trace(unsigned long long *out, int n) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_roles_trace), sizeof(unsigned long long) * (n < 128 ? n : 128));
+}
+#endif
 
 #ifdef BAMD_LAT_TRACE
 extern "C" int bamd_debug_lat_trace(unsigned long long *out, int n) {
