@@ -21,6 +21,7 @@
 // into the canonical state-dict layout: bitwise reproducible.
 #include "fused.hpp"
 
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -3742,6 +3743,9 @@ __global__ void __launch_bounds__(256) pack_k(const float *__restrict__ params, 
 
 // ---- host side ------------------------------------------------------------------------------------------
 struct FusedOps;
+// wide models in the bf16 mode: the bf16 fragment sets of a handle -- W0 / W7 / W7^T (training) / W0 in the DMA encode's k order / the
+// narrow encoder layers 1..3 / the narrow decoder layers 4..6 (chain_bf16_pair)
+enum WbSlot { WB_W0, WB_W7, WB_W7T, WB_W0_DMA, WB_CHAIN_ENC, WB_CHAIN_DEC, WB_SLOTS };
 struct FusedState {
     const FusedOps *ops = nullptr;
     DevBuf pack_src;   // int per packed float: canonical parameter index or -1
@@ -3758,9 +3762,8 @@ struct FusedState {
     // 256 16.6 / 21.9, 512 18.0 / 23.4, 1024 21.7 / 27.0, 2048 33.1 / 34.1, 4096 53.6 / 44.1 (every workgroup streams all
     // weights: 4x the L2 traffic of the 16-row chain)
     int64_t lat4_max_rows = 2048;
-    DevBuf wb_src[6], wb[6];           // wide models in the bf16 mode: index maps and bf16 fragments of W0 / W7 / W7^T (training) / W0 in the DMA encode's
-                                       // k order / the narrow encoder layers 1..3 / the narrow decoder layers 4..6 (chain_bf16_pair)
-    int wb_count[6] = {0, 0, 0, 0, 0, 0};
+    DevBuf wb_src[WB_SLOTS], wb[WB_SLOTS];      // wide models in the bf16 mode: index maps and bf16 fragments, one per WbSlot
+    int wb_count[WB_SLOTS] = {};
     bool wb_stale = false;             // the bf16 fragments lag the parameters (re-rounded before the next encode / decode)
     bool packed_stale = false;         // handles with a second state (64..127 columns): an optimiser step refreshed the small-batch state's fragments only
     bool dz16 = false;                 // this pass stores dL/drecon as bfloat16 (set per pass by the layer-wise driver: fused_wide_set_dz16)
@@ -3907,7 +3910,22 @@ struct FusedOps {
 
 static FusedState *state_of(bamd_handle *h) { return (FusedState *)h->fused_state; }
 
-static constexpr bool infer_pair() { return true; }   // two 16-row tiles per wave in encode / decode (+5.5 % / +7 % over one tile)
+// a run-time bool as a template argument: fn(std::true_type / std::false_type)
+template <class Fn> static void with_bool(bool b, Fn &&fn) {
+    if (b) fn(std::true_type{});
+    else fn(std::false_type{});
+}
+
+// Does Net<F, Z> serve this handle?  An exact instantiation: all nine widths.  A class (run-time widths): the hidden widths, and
+// f_min .. F columns with a latent of z_min .. Z.
+template <int F, int Z> static bool net_matches(const bamd_handle *h, bool cls, int f_min, int z_min) {
+    using N = Net<F, Z>;
+    if (h->L != 8) return false;
+    for (int i = 0; i <= 8; ++i)
+        if (!(cls && i % 4 == 0) && h->dims[i] != N::dim(i)) return false;
+    return !cls || (h->dims[0] == h->dims[8] && h->dims[0] >= f_min && h->dims[0] <= F && h->dims[4] >= z_min && h->dims[4] <= Z);
+}
+
 static int infer_grid(int64_t n) {
     int64_t wg = ((n + 15) / 16 + 3) / 4;
     return (int)(wg < 1 ? 1 : (wg > 1024 ? 1024 : wg));
@@ -3923,17 +3941,7 @@ constexpr int kTrainRolesDefault = 1;
 // the class's extra slots empty (build_maps).  Same kernels, same tile counts as the 24-column instantiation for 16..31 columns.
 template <int F, int Z, bool RT = false> struct Impl {
     using N = Net<F, Z>;
-    static bool matches(const bamd_handle *h) {
-        if (h->L != 8) return false;
-        if (RT) {
-            for (int i = 1; i <= 7; ++i)
-                if (i != 4 && h->dims[i] != N::dim(i)) return false;
-            return h->dims[0] == h->dims[8] && h->dims[0] >= 1 && h->dims[0] <= F && h->dims[4] >= 1 && h->dims[4] <= Z;
-        }
-        for (int i = 0; i <= 8; ++i)
-            if (h->dims[i] != N::dim(i)) return false;
-        return true;
-    }
+    static bool matches(const bamd_handle *h) { return net_matches<F, Z>(h, RT, 1, 1); }
     static constexpr int train_lds = (img_a_rows<N>() + kImgB) * kQS * (int)sizeof(float) + (train_bias_in_lds<N>() ? (N::bf_off(8) - N::bf_off(0)) * 16 : 0);      // images (+ bias fragments)
     // the role-split pair needs its chain role inside 256 registers: the two-tile inputs (the 24-column models, the 31-column class)
     static constexpr bool train_roles = !RT && tiles(F) <= 2;
@@ -3954,29 +3962,25 @@ template <int F, int Z, bool RT = false> struct Impl {
     }
     static int encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype,
                       hipStream_t s) {
-        constexpr int extra_lds = 0;
-        if (F <= 64 && infer_pair()) {
-            hipLaunchKernelGGL((infer2_kernel<F <= 64 ? F : 24, Z, K_ENCODE, RT>), dim3(infer_grid((n + 1) / 2)), dim3(256), 0, s,
+        // up to 64 columns: two 16-row tiles per wave in encode / decode (+5.5 % / +7 % over one tile)
+        if constexpr (F <= 64)
+            hipLaunchKernelGGL((infer2_kernel<F, Z, K_ENCODE, RT>), dim3(infer_grid((n + 1) / 2)), dim3(256), 0, s,
                                (const v4 *)h->packed.p, x, x_dtype == BAMD_F64, n, features, z, z_dtype,
                                (const uint8_t *)nullptr, fr(h), zr(h));
-            BAMD_HIP(hipGetLastError());
-            return BAMD_OK;
-        }
-        hipLaunchKernelGGL((infer_kernel<F, Z, K_ENCODE, RT>), dim3(infer_grid(n)), dim3(256), extra_lds, s, (const v4 *)h->packed.p, x,
-                           x_dtype == BAMD_F64, n, features, z, z_dtype, (const uint8_t *)nullptr, (double *)nullptr, fr(h), zr(h));
+        else
+            hipLaunchKernelGGL((infer_kernel<F, Z, K_ENCODE, RT>), dim3(infer_grid(n)), dim3(256), 0, s, (const v4 *)h->packed.p, x,
+                               x_dtype == BAMD_F64, n, features, z, z_dtype, (const uint8_t *)nullptr, (double *)nullptr, fr(h), zr(h));
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
     static int decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features, const uint8_t *int_mask,
                       void *out, int out_dtype, hipStream_t s) {
-        if (F <= 64 && infer_pair()) {
-            hipLaunchKernelGGL((infer2_kernel<F <= 64 ? F : 24, Z, K_DECODE, RT>), dim3(infer_grid((n + 1) / 2)), dim3(256), 0, s,
+        if constexpr (F <= 64)
+            hipLaunchKernelGGL((infer2_kernel<F, Z, K_DECODE, RT>), dim3(infer_grid((n + 1) / 2)), dim3(256), 0, s,
                                (const v4 *)h->packed.p, z, z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, fr(h), zr(h));
-            BAMD_HIP(hipGetLastError());
-            return BAMD_OK;
-        }
-        hipLaunchKernelGGL((infer_kernel<F, Z, K_DECODE, RT>), dim3(infer_grid(n)), dim3(256), 0, s, (const v4 *)h->packed.p, z,
-                           z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, (double *)nullptr, fr(h), zr(h));
+        else
+            hipLaunchKernelGGL((infer_kernel<F, Z, K_DECODE, RT>), dim3(infer_grid(n)), dim3(256), 0, s, (const v4 *)h->packed.p, z,
+                               z_dtype, n, features, out, out_dtype == BAMD_F64, int_mask, (double *)nullptr, fr(h), zr(h));
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
@@ -4146,6 +4150,57 @@ template <int F, int Z, bool SMALL = true> struct ImplInferClass {
     }
 };
 
+// Wide models, the row loops of encode / decode / forward_loss: chunk after chunk, through the float32 staging buffer h->work where the
+// kernels cannot take the caller's rows as they are.
+constexpr int64_t kChunkRows = 1 << 18;     // staging chunk: 2.6 GB of float32 rows
+// Input side: normalise-on-load with `features`; `to_f32`: a plain conversion of rows that are not float32 (forward_loss, whose kernels
+// read float32 only).  launch(src, src_is_f64, rows, r0) issues the kernels of the chunk that starts at row r0.
+template <class Launch>
+static int wide_in_chunks(bamd_handle *h, const void *x, int x_dtype, int64_t n, int fr, const double *features, int64_t chunk, bool to_f32,
+                          hipStream_t s, Launch &&launch) {
+    const size_t xes = dtype_bytes(x_dtype);
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
+        const void *src = (const char *)x + (size_t)r0 * fr * xes;
+        int src_f64 = x_dtype == BAMD_F64;
+        if (features || (to_f32 && x_dtype != BAMD_F32)) {
+            int rc = h->work.ensure((size_t)rows * fr * sizeof(float));
+            if (rc) return rc;
+            rc = features ? launch_normalize(src, x_dtype, rows, fr, features, h->work.p, BAMD_F32, s)
+                          : launch_convert(src, x_dtype, h->work.p, BAMD_F32, rows * fr, s);
+            if (rc) return rc;
+            src = h->work.p;
+            src_f64 = 0;
+        }
+        if (const int rc = launch(src, src_f64, rows, r0)) return rc;
+    }
+    return BAMD_OK;
+}
+// Output side (decode): launch(z_chunk, rows, kout, kout_is_f64) writes the chunk's rows to kout -- the caller's rows, or the staging
+// buffer, which launch_renormalize then turns into the caller's float64 rows.
+template <class Launch>
+static int wide_out_chunks(bamd_handle *h, const void *z, int z_dtype, int zr, int64_t n, int fr, const double *features,
+                           const uint8_t *int_mask, void *out, int out_dtype, hipStream_t s, Launch &&launch) {
+    const size_t zes = dtype_bytes(z_dtype), oes = dtype_bytes(out_dtype);
+    if (features && out_dtype != BAMD_F64) { set_error("decode with features needs a float64 output"); return BAMD_ERR_INVALID; }
+    for (int64_t r0 = 0; r0 < n; r0 += kChunkRows) {
+        const int64_t rows = n - r0 < kChunkRows ? n - r0 : kChunkRows;
+        void *dst = (char *)out + (size_t)r0 * fr * oes;
+        if (features) {
+            int rc = h->work.ensure((size_t)rows * fr * sizeof(float));
+            if (rc) return rc;
+        }
+        void *kout = features ? h->work.p : dst;
+        launch((const void *)((const char *)z + (size_t)r0 * zr * zes), rows, kout, !features && out_dtype == BAMD_F64);
+        if (features) {
+            int rc = launch_renormalize(kout, BAMD_F32, rows, fr, features, int_mask, (double *)dst, s);
+            if (rc) return rc;
+        }
+    }
+    BAMD_HIP(hipGetLastError());
+    return BAMD_OK;
+}
+
 // Wide models (CFD_dense_AE(2500, 25), BASELINE.json configs[3]): encode and decode as ONE launch each (wide_encode_lds_kernel / wide_encode2_kernel, wide_decode_lds_kernel);
 // training = the two row-local launches wide_fwd / wide_bwd inside generic.hip's layer-wise pass (the weight gradient of a
 // 2500 x 200 layer is 2 MB of accumulators per workgroup: it has to be a split-K product, generic.hip's dw_wide_k); forward_loss
@@ -4157,20 +4212,9 @@ template <int F, int Z, bool SMALL = true> struct ImplInferClass {
 // with LDS-shared fragments serve every size of such a handle.
 template <int F, int Z, bool WRT = false> struct ImplWide {
     using N = Net<F, Z>;
-    static constexpr int64_t kChunkRows = 1 << 18;     // staging chunk: 2.6 GB of float32 rows
     static int Fr(const bamd_handle *h) { return WRT ? h->dims[0] : F; }
     static int Zr(const bamd_handle *h) { return WRT ? h->dims[4] : Z; }
-    static bool matches(const bamd_handle *h) {
-        if (h->L != 8) return false;
-        if (WRT) {
-            for (int i = 1; i <= 7; ++i)
-                if (i != 4 && h->dims[i] != N::dim(i)) return false;
-            return h->dims[0] == h->dims[8] && h->dims[0] >= 48 && h->dims[0] <= F && h->dims[4] <= Z;
-        }
-        for (int i = 0; i <= 8; ++i)
-            if (h->dims[i] != N::dim(i)) return false;
-        return true;
-    }
+    static bool matches(const bamd_handle *h) { return net_matches<F, Z>(h, WRT, 48, INT_MIN); }      // (no lower bound on the latent)
     static_assert(!WRT || F % 16 == 0, "a wide class width is a multiple of 16 (every class chunk a full tile)");
     static int setup(bamd_handle *h, FusedState *st) { return build_maps<F, Z, false>(h, st); }
     static int grid_for(int64_t n) {
@@ -4179,80 +4223,47 @@ template <int F, int Z, bool WRT = false> struct ImplWide {
     }
     static int encode(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *z, int z_dtype,
                       hipStream_t s) {
-        const size_t xes = dtype_bytes(x_dtype), zes = dtype_bytes(z_dtype);
-        const int fr = Fr(h), zr = Zr(h);
-        for (int64_t r0 = 0; r0 < n; r0 += kChunkRows) {
-            const int64_t rows = n - r0 < kChunkRows ? n - r0 : kChunkRows;
-            const void *src = (const char *)x + (size_t)r0 * fr * xes;
-            int src_f64 = x_dtype == BAMD_F64;
-            if (features) {
-                int rc = h->work.ensure((size_t)rows * fr * sizeof(float));
-                if (rc) return rc;
-                rc = launch_normalize(src, x_dtype, rows, fr, features, h->work.p, BAMD_F32, s);
-                if (rc) return rc;
-                src = h->work.p;
-                src_f64 = 0;
-            }
+        const size_t zes = dtype_bytes(z_dtype);
+        const int fr = Fr(h), zr = Zr(h), z64 = z_dtype == BAMD_F64;
+        const int rc = wide_in_chunks(h, x, x_dtype, n, fr, features, kChunkRows, false, s, [&](const void *src, int src_f64, int64_t rows, int64_t r0) -> int {
             // two row tiles per wave once that still leaves two workgroups per CU (measured: 512-column model, 524288 rows
             // 384 -> 419 M rows/s; C4 131072 frames 87.6 -> 91.8 M, but 32768 frames 96 -> 72 M: half the chip's wave slots empty);
             // BALER_AMD_WIDE2=0 / 1 forces one / two tiles
             const char *e2 = getenv("BALER_AMD_WIDE2");
             const bool two = !WRT && (e2 ? e2[0] == '1' : rows >= 32 * 4 * 512);
             void *zo = (void *)((char *)z + (size_t)r0 * zr * zes);
-            const int z64 = z_dtype == BAMD_F64;
-            if constexpr (!WRT) {
-                if (two && src_f64)
-                    hipLaunchKernelGGL((wide_encode2_kernel<F, Z, true>), dim3(grid_for((rows + 1) / 2)), dim3(256), 0, s, (const v4 *)h->packed.p, src, rows, zo, z64);
-                else if (two)
-                    hipLaunchKernelGGL((wide_encode2_kernel<F, Z, false>), dim3(grid_for((rows + 1) / 2)), dim3(256), 0, s, (const v4 *)h->packed.p, src, rows, zo, z64);
-            }
-            if (!two) {
-                // fragments shared through LDS (C4, 32768 frames: 92.5 -> 98.5 M rows/s against per-wave fragments)
-                const int64_t ng = (rows + 63) / 64;
-                const dim3 gl((unsigned)(ng > 2048 ? 2048 : ng));
-                if (src_f64) hipLaunchKernelGGL((wide_encode_lds_kernel<F, Z, true, WRT>), gl, dim3(256), 0, s, (const v4 *)h->packed.p, src, rows, zo, z64, fr, zr);
-                else hipLaunchKernelGGL((wide_encode_lds_kernel<F, Z, false, WRT>), gl, dim3(256), 0, s, (const v4 *)h->packed.p, src, rows, zo, z64, fr, zr);
-            }
-        }
+            with_bool(src_f64, [&](auto in64) {
+                constexpr bool IN64 = decltype(in64)::value;
+                if constexpr (!WRT)
+                    if (two) hipLaunchKernelGGL((wide_encode2_kernel<F, Z, IN64>), dim3(grid_for((rows + 1) / 2)), dim3(256), 0, s, (const v4 *)h->packed.p, src, rows, zo, z64);
+                if (!two) {
+                    // fragments shared through LDS (C4, 32768 frames: 92.5 -> 98.5 M rows/s against per-wave fragments)
+                    const int64_t ng = (rows + 63) / 64;
+                    const dim3 gl((unsigned)(ng > 2048 ? 2048 : ng));
+                    hipLaunchKernelGGL((wide_encode_lds_kernel<F, Z, IN64, WRT>), gl, dim3(256), 0, s, (const v4 *)h->packed.p, src, rows, zo, z64, fr, zr);
+                }
+            });
+            return BAMD_OK;
+        });
+        if (rc) return rc;
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
     static int decode(bamd_handle *h, const void *z, int z_dtype, int64_t n, const double *features, const uint8_t *int_mask,
                       void *out, int out_dtype, hipStream_t s) {
-        const size_t zes = dtype_bytes(z_dtype), oes = dtype_bytes(out_dtype);
-        if (features && out_dtype != BAMD_F64) { set_error("decode with features needs a float64 output"); return BAMD_ERR_INVALID; }
         const int fr = Fr(h), zr = Zr(h);
-        for (int64_t r0 = 0; r0 < n; r0 += kChunkRows) {
-            const int64_t rows = n - r0 < kChunkRows ? n - r0 : kChunkRows;
-            void *dst = (char *)out + (size_t)r0 * fr * oes;
-            void *kout = dst;
-            int kout_f64 = out_dtype == BAMD_F64;
-            if (features) {
-                int rc = h->work.ensure((size_t)rows * fr * sizeof(float));
-                if (rc) return rc;
-                kout = h->work.p;
-                kout_f64 = 0;
-            }
-            const void *zi = (const void *)((const char *)z + (size_t)r0 * zr * zes);
-            if (kout_f64)
-                hipLaunchKernelGGL((wide_decode_lds_kernel<F, Z, true, WRT>), dim3(grid_for(rows)), dim3(256), 0, s, (const v4 *)h->packed.p, zi,
-                                   z_dtype == BAMD_F64, rows, kout, fr, zr);
-            else
-                hipLaunchKernelGGL((wide_decode_lds_kernel<F, Z, false, WRT>), dim3(grid_for(rows)), dim3(256), 0, s, (const v4 *)h->packed.p, zi,
-                                   z_dtype == BAMD_F64, rows, kout, fr, zr);
-            if (features) {
-                int rc = launch_renormalize(kout, BAMD_F32, rows, fr, features, int_mask, (double *)dst, s);
-                if (rc) return rc;
-            }
-        }
-        BAMD_HIP(hipGetLastError());
-        return BAMD_OK;
+        return wide_out_chunks(h, z, z_dtype, zr, n, fr, features, int_mask, out, out_dtype, s, [&](const void *zi, int64_t rows, void *kout, bool kout_f64) {
+            with_bool(kout_f64, [&](auto out64) {
+                hipLaunchKernelGGL((wide_decode_lds_kernel<F, Z, decltype(out64)::value, WRT>), dim3(grid_for(rows)), dim3(256), 0, s,
+                                   (const v4 *)h->packed.p, zi, z_dtype == BAMD_F64, rows, kout, fr, zr);
+            });
+        });
     }
     // y[l] = activations entering layer l (row-major float32, y[0] unused), dz[l] = dL/d(pre-activation of layer l)
     // Small training batches (up to BALER_AMD_WIDE_SMALL_ROWS rows, default 8192): how many workgroups share the wide dimension of one
     // 64-row group (wide_small_in_kernel / wide_small_out_kernel); 1 = the one-launch kernels.  At least three chunks / tiles per
     // workgroup, at most 16 splits (the MID launches add the partial sums of every split).
-    static int small_splits(const bamd_handle *h, int64_t rows, int units, int *per) {
+    static int small_splits(int64_t rows, int units, int *per) {
         const int64_t lim = env_ll("BALER_AMD_WIDE_SMALL_ROWS", 8192);
         *per = units;
         if (rows > lim) return 1;
@@ -4279,36 +4290,66 @@ template <int F, int Z, bool WRT = false> struct ImplWide {
     static int64_t out16_rows() {     // BALER_AMD_WIDE_OUT16_ROWS: most rows whose tile-split product (de4) takes one 16-row tile per workgroup
         return env_ll("BALER_AMD_WIDE_OUT16_ROWS", 512);
     }
-    static bool small_pass(const bamd_handle *h, int64_t rows) {      // this batch runs on the split launches
-        int per = 0;
-        return Fr(h) / 16 >= 3 && small_splits(h, rows, Fr(h) / 16, &per) > 1 && small_splits(h, rows, (Fr(h) + 15) / 16, &per) > 1;
+    // The split launches of one batch, decided once per call.
+    struct SmallPlan {
+        int ngroup;           // 64-row groups
+        int s_in, cps;        // contraction-split products (en1, de4's input gradient): splits, 16-column chunks per split
+        int s_out, tps;       // tile-split product (de4): splits, output tiles per split
+        bool in16, out16;     // one 16-row tile per workgroup instead of one 64-row group
+        bool chunks3;         // the wide dimension has the three chunks a split needs
+        // wide_fwd, forward_loss and small_pass split when BOTH products split; wide_bwd asks for s_in alone.  The two may differ, and
+        // harmlessly: wide_bwd runs its own in-product into wpart, it reads nothing that the forward's split launches left there.
+        bool fwd() const { return s_in > 1 && s_out > 1 && chunks3; }
+        bool bwd() const { return s_in > 1 && chunks3; }
+        size_t part_bytes() const { return (size_t)s_in * ngroup * 4 * 13 * 64 * sizeof(v4); }
+    };
+    static SmallPlan small_plan(const bamd_handle *h, int64_t rows) {
+        SmallPlan p{};
+        const int fr = Fr(h);
+        p.ngroup = (int)((rows + 63) / 64);
+        p.s_in = small_splits(rows, fr / 16, &p.cps);
+        p.s_out = small_splits(rows, (fr + 15) / 16, &p.tps);
+        p.in16 = p.s_in > 1 && rows <= in16_rows();
+        p.out16 = p.s_out > 1 && rows <= out16_rows();
+        p.chunks3 = fr / 16 >= 3;
+        return p;
+    }
+    static bool small_pass(const bamd_handle *h, int64_t rows) { return small_plan(h, rows).fwd(); }      // this batch runs on the split launches
+    // src x frags -> s_in partial sets at the front of wpart (`behind`: bytes the caller keeps behind them)
+    static int launch_small_in(bamd_handle *h, const SmallPlan &p, const v4 *frags, int count, const float *src, int64_t rows, hipStream_t s,
+                               size_t behind = 0) {
+        FusedState *st = state_of(h);
+        const int rc = st->wpart.ensure(p.part_bytes() + behind);
+        if (rc) return rc;
+        if (p.in16)
+            hipLaunchKernelGGL((wide_small_in16_kernel<F, WRT>), dim3(p.s_in, (unsigned)(4 * p.ngroup)), dim3(256), 0, s, frags, count, src, rows,
+                               (v4 *)st->wpart.p, p.cps, Fr(h));
+        else
+            hipLaunchKernelGGL((wide_small_in_kernel<F, WRT>), dim3(p.s_in, p.ngroup), dim3(256), 0, s, frags, count, src, rows, (v4 *)st->wpart.p, p.cps, Fr(h));
+        return BAMD_OK;
+    }
+    // de4 + loss of y7 in s_out tile ranges; TRAIN: dL/drecon into dst, else the reconstruction (dst may be null).  Returns the number of loss partials.
+    template <bool TRAIN>
+    static int launch_small_out(bamd_handle *h, const SmallPlan &p, const float *x, int64_t rows, const float *y7, void *dst, double *loss_part,
+                                int out_f64, hipStream_t s) {
+        if (p.out16)
+            hipLaunchKernelGGL((wide_small_out16_kernel<F, Z, WRT, TRAIN>), dim3(p.s_out, (unsigned)(4 * p.ngroup)), dim3(256), 0, s, (const v4 *)h->packed.p, x,
+                               rows, y7, dst, loss_part, p.tps, Fr(h), out_f64);
+        else
+            hipLaunchKernelGGL((wide_small_out_kernel<F, Z, WRT, TRAIN>), dim3(p.s_out, p.ngroup), dim3(256), 0, s, (const v4 *)h->packed.p, x, rows, y7, dst,
+                               loss_part, p.tps, Fr(h), out_f64);
+        return p.s_out * p.ngroup * (p.out16 ? 4 : 1);
     }
     static int wide_fwd(bamd_handle *h, const float *x, int64_t rows, float *const *y, float *dz_last, double *loss_part, int *nblk,
                         hipStream_t s) {
         const int grid = grid_for(rows);
-        int cps = 0, tps = 0;
-        const int fr = Fr(h), ngroup = (int)((rows + 63) / 64);
-        const int s_in = small_splits(h, rows, fr / 16, &cps), s_out = small_splits(h, rows, (fr + 15) / 16, &tps);
-        if (s_in > 1 && s_out > 1 && fr / 16 >= 3) {
-            FusedState *st = state_of(h);
-            int rc = st->wpart.ensure((size_t)s_in * ngroup * 4 * 13 * 64 * sizeof(v4));
+        const SmallPlan p = small_plan(h, rows);
+        if (p.fwd()) {
+            const int rc = launch_small_in(h, p, (const v4 *)h->packed.p + N::wf_off(0), N::wcount(0), x, rows, s);
             if (rc) return rc;
-            if (rows <= in16_rows())
-                hipLaunchKernelGGL((wide_small_in16_kernel<F, WRT>), dim3(s_in, (unsigned)(4 * ngroup)), dim3(256), 0, s, (const v4 *)h->packed.p + N::wf_off(0),
-                                   N::wcount(0), x, rows, (v4 *)st->wpart.p, cps, fr);
-            else
-                hipLaunchKernelGGL((wide_small_in_kernel<F, WRT>), dim3(s_in, ngroup), dim3(256), 0, s, (const v4 *)h->packed.p + N::wf_off(0), N::wcount(0), x, rows,
-                                   (v4 *)st->wpart.p, cps, fr);
             hipLaunchKernelGGL((wide_train_fwd_kernel<F, Z, true, WRT, true>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p, x, rows, y[1], y[2],
-                               y[3], y[4], y[5], y[6], y[7], (void *)dz_last, 0, loss_part, fr, Zr(h), (const v4 *)st->wpart.p, s_in);
-            const bool out16 = rows <= out16_rows();
-            if (out16)
-                hipLaunchKernelGGL((wide_small_out16_kernel<F, Z, WRT>), dim3(s_out, (unsigned)(4 * ngroup)), dim3(256), 0, s, (const v4 *)h->packed.p, x, rows,
-                                   (const float *)y[7], (void *)dz_last, loss_part, tps, fr, 0);
-            else
-                hipLaunchKernelGGL((wide_small_out_kernel<F, Z, WRT>), dim3(s_out, ngroup), dim3(256), 0, s, (const v4 *)h->packed.p, x, rows, (const float *)y[7],
-                                   (void *)dz_last, loss_part, tps, fr, 0);
-            *nblk = s_out * ngroup * (out16 ? 4 : 1);
+                               y[3], y[4], y[5], y[6], y[7], (void *)dz_last, 0, loss_part, Fr(h), Zr(h), (const v4 *)state_of(h)->wpart.p, p.s_in);
+            *nblk = launch_small_out<true>(h, p, x, rows, y[7], dz_last, loss_part, 0, s);
             BAMD_HIP(hipGetLastError());
             return BAMD_OK;
         }
@@ -4322,80 +4363,49 @@ template <int F, int Z, bool WRT = false> struct ImplWide {
     // normalise-on-load, as in encode)
     static int forward_loss(bamd_handle *h, const void *x, int x_dtype, int64_t n, const double *features, void *recon, int recon_dtype,
                             double *loss_sum, hipStream_t s) {
-        const size_t xes = dtype_bytes(x_dtype), oes = dtype_bytes(recon_dtype);
-        const int fr = Fr(h), zr = Zr(h);
+        const size_t oes = dtype_bytes(recon_dtype);
+        const int fr = Fr(h), zr = Zr(h), r64 = recon_dtype == BAMD_F64;
         const int64_t chunk = 1 << 16;
         int rc = h->lossp.ensure(sizeof(double) * 4096 * ((n + chunk - 1) / chunk > 0 ? (n + chunk - 1) / chunk : 1));
         if (rc) return rc;
         int nblk = 0;
-        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-            const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
-            const void *src = (const char *)x + (size_t)r0 * fr * xes;
-            if (features || x_dtype != BAMD_F32) {
-                rc = h->work.ensure((size_t)rows * fr * sizeof(float));
-                if (rc) return rc;
-                rc = features ? launch_normalize(src, x_dtype, rows, fr, features, h->work.p, BAMD_F32, s)
-                              : launch_convert(src, x_dtype, h->work.p, BAMD_F32, rows * fr, s);
-                if (rc) return rc;
-                src = h->work.p;
-            }
+        rc = wide_in_chunks(h, x, x_dtype, n, fr, features, chunk, true, s, [&](const void *srcv, int, int64_t rows, int64_t r0) -> int {
+            const float *src = (const float *)srcv;
             const int grid = grid_for(rows);
             void *rdst = recon ? (void *)((char *)recon + (size_t)r0 * fr * oes) : nullptr;
-            if (small_pass(h, rows)) {      // validation batches of the reference's sizes (60 rows ...): the split launches (see wide_fwd)
-                FusedState *st = state_of(h);
-                int cps = 0, tps = 0;
-                const int ngroup = (int)((rows + 63) / 64);
-                const int s_in = small_splits(h, rows, fr / 16, &cps), s_out = small_splits(h, rows, (fr + 15) / 16, &tps);
-                rc = st->wpart.ensure((size_t)s_in * ngroup * 4 * 13 * 64 * sizeof(v4) + (size_t)ngroup * 64 * 200 * sizeof(float));
+            double *lossp = (double *)h->lossp.p + nblk;
+            const SmallPlan p = small_plan(h, rows);
+            if (p.fwd()) {      // validation batches of the reference's sizes (60 rows ...): the split launches (see wide_fwd), y7 behind the partial sets
+                const int rc = launch_small_in(h, p, (const v4 *)h->packed.p + N::wf_off(0), N::wcount(0), src, rows, s, (size_t)p.ngroup * 64 * 200 * sizeof(float));
                 if (rc) return rc;
-                float *y7 = (float *)((char *)st->wpart.p + (size_t)s_in * ngroup * 4 * 13 * 64 * sizeof(v4));
-                if (rows <= in16_rows())
-                    hipLaunchKernelGGL((wide_small_in16_kernel<F, WRT>), dim3(s_in, (unsigned)(4 * ngroup)), dim3(256), 0, s,
-                                       (const v4 *)h->packed.p + N::wf_off(0), N::wcount(0), (const float *)src, rows, (v4 *)st->wpart.p, cps, fr);
-                else
-                    hipLaunchKernelGGL((wide_small_in_kernel<F, WRT>), dim3(s_in, ngroup), dim3(256), 0, s, (const v4 *)h->packed.p + N::wf_off(0), N::wcount(0),
-                                       (const float *)src, rows, (v4 *)st->wpart.p, cps, fr);
-                hipLaunchKernelGGL((wide_train_fwd_kernel<F, Z, false, WRT, true>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p, (const float *)src,
+                const char *wpart = (const char *)state_of(h)->wpart.p;
+                float *y7 = (float *)(wpart + p.part_bytes());
+                hipLaunchKernelGGL((wide_train_fwd_kernel<F, Z, false, WRT, true>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p, src,
                                    rows, (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, y7,
-                                   (void *)nullptr, 0, (double *)nullptr, fr, zr, (const v4 *)st->wpart.p, s_in);
-                const bool out16 = rows <= out16_rows();
-                if (out16)
-                    hipLaunchKernelGGL((wide_small_out16_kernel<F, Z, WRT, false>), dim3(s_out, (unsigned)(4 * ngroup)), dim3(256), 0, s, (const v4 *)h->packed.p,
-                                       (const float *)src, rows, (const float *)y7, rdst, (double *)h->lossp.p + nblk, tps, fr, recon_dtype == BAMD_F64 ? 1 : 0);
-                else
-                    hipLaunchKernelGGL((wide_small_out_kernel<F, Z, WRT, false>), dim3(s_out, ngroup), dim3(256), 0, s, (const v4 *)h->packed.p, (const float *)src,
-                                       rows, (const float *)y7, rdst, (double *)h->lossp.p + nblk, tps, fr, recon_dtype == BAMD_F64 ? 1 : 0);
-                nblk += s_out * ngroup * (out16 ? 4 : 1);
-                continue;
+                                   (void *)nullptr, 0, (double *)nullptr, fr, zr, (const v4 *)wpart, p.s_in);
+                nblk += launch_small_out<false>(h, p, src, rows, y7, rdst, lossp, r64, s);
+                return BAMD_OK;
             }
-            hipLaunchKernelGGL((wide_train_fwd_kernel<F, Z, false, WRT>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p, (const float *)src,
+            hipLaunchKernelGGL((wide_train_fwd_kernel<F, Z, false, WRT>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p, src,
                                rows, (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr,
-                               (float *)nullptr, (float *)nullptr, rdst,
-                               recon_dtype == BAMD_F64, (double *)h->lossp.p + nblk, fr, zr);
+                               (float *)nullptr, (float *)nullptr, rdst, r64, lossp, fr, zr);
             nblk += grid;
-        }
+            return BAMD_OK;
+        });
+        if (rc) return rc;
         hipLaunchKernelGGL(sum_partials_fixed_k<double>, dim3(1), dim3(256), 0, s, (const double *)h->lossp.p, nblk, 1.0 / fr, loss_sum, 0);
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
     static int wide_bwd(bamd_handle *h, int64_t rows, float *const *y, float *const *dz, const float *dz_latent, hipStream_t s) {
-        int cps = 0;
-        const int fr = Fr(h), ngroup = (int)((rows + 63) / 64);
-        const int s_in = small_splits(h, rows, fr / 16, &cps);
-        if (s_in > 1 && fr / 16 >= 3) {      // small batches: de4's input-gradient product split over the wide dimension (see wide_fwd)
-            FusedState *st = state_of(h);
-            int rc = st->wpart.ensure((size_t)s_in * ngroup * 4 * 13 * 64 * sizeof(v4));
+        const SmallPlan p = small_plan(h, rows);
+        if (p.bwd()) {      // small batches: de4's input-gradient product split over the wide dimension (see wide_fwd)
+            const int rc = launch_small_in(h, p, (const v4 *)h->packed.p + N::wb_off(7), N::wcount(7), (const float *)dz[7], rows, s);
             if (rc) return rc;
-            if (rows <= in16_rows())
-                hipLaunchKernelGGL((wide_small_in16_kernel<F, WRT>), dim3(s_in, (unsigned)(4 * ngroup)), dim3(256), 0, s, (const v4 *)h->packed.p + N::wb_off(7),
-                                   N::wcount(7), (const float *)dz[7], rows, (v4 *)st->wpart.p, cps, fr);
-            else
-                hipLaunchKernelGGL((wide_small_in_kernel<F, WRT>), dim3(s_in, ngroup), dim3(256), 0, s, (const v4 *)h->packed.p + N::wb_off(7), N::wcount(7),
-                                   (const float *)dz[7], rows, (v4 *)st->wpart.p, cps, fr);
             hipLaunchKernelGGL((wide_train_bwd_kernel<F, Z, WRT, true>), dim3(grid_for(rows)), dim3(256), 0, s, (const v4 *)h->packed.p,
                                (const float *)dz[7], rows, (const float *)y[1], (const float *)y[2], (const float *)y[3], (const float *)y[5],
-                               (const float *)y[6], (const float *)y[7], dz[0], dz[1], dz[2], dz[3], dz[4], dz[5], dz[6], dz_latent, fr, Zr(h),
-                               (const v4 *)st->wpart.p, s_in);
+                               (const float *)y[6], (const float *)y[7], dz[0], dz[1], dz[2], dz[3], dz[4], dz[5], dz[6], dz_latent, Fr(h), Zr(h),
+                               (const v4 *)state_of(h)->wpart.p, p.s_in);
             BAMD_HIP(hipGetLastError());
             return BAMD_OK;
         }
@@ -4428,82 +4438,64 @@ template <int F, int Z> struct ImplWideBf16 {
     static int setup(bamd_handle *h, FusedState *st) {
         int rc = build_maps<F, Z, false>(h, st);
         if (rc) return rc;
-        std::vector<int> s0((size_t)KB * 13 * 64 * 8, -1), s7((size_t)KT * 7 * 64 * 8, -1);
-        for (int c = 0; c < KB; ++c)
-            for (int t = 0; t < 13; ++t)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int i = lane & 15, g = lane >> 4;
-                        const int nf = slot_feature(200, t, i / 4, i % 4), kf = 32 * c + 8 * g + j;
-                        if (nf >= 0 && kf < F) s0[(((size_t)c * 13 + t) * 64 + lane) * 8 + j] = N::w_off(0) + nf * F + kf;
-                    }
-        for (int t = 0; t < KT; ++t)
-            for (int c = 0; c < 7; ++c)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int i = lane & 15, g = lane >> 4, q = 2 * c + j / 4;
-                        const int nf = slot_feature(F, t, i / 4, i % 4), kf = q < 13 ? slot_feature(200, q, g, j % 4) : -1;
-                        if (nf >= 0 && kf >= 0) s7[(((size_t)t * 7 + c) * 64 + lane) * 8 + j] = N::w_off(7) + nf * 200 + kf;
-                    }
-        // W7^T for the input-gradient product of training, in en1's [chunk of 32 wide features][tile of the 200 side] order
-        std::vector<int> s7t((size_t)KB * 13 * 64 * 8, -1);
-        for (int c = 0; c < KB; ++c)
-            for (int t = 0; t < 13; ++t)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int i = lane & 15, g = lane >> 4;
-                        const int nf = slot_feature(200, t, i / 4, i % 4), kf = 32 * c + 8 * g + j;
-                        if (nf >= 0 && kf < F) s7t[(((size_t)c * 13 + t) * 64 + lane) * 8 + j] = N::w_off(7) + kf * 200 + nf;
-                    }
-        // W0 once more for the DMA encode kernel: full chunks in ITS k order -- k slot (g, j) <-> feature 16 (j >> 2) + 4 g + (j & 3) of the
-        // chunk, what a lane holds after reading bytes 16 g .. + 15 of each 64-byte half of the row's chunk; a partial last chunk natural
-        std::vector<int> s0p((size_t)KB * 13 * 64 * 8, -1);
-        for (int c = 0; c < KB; ++c)
-            for (int t = 0; t < 13; ++t)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int i = lane & 15, g = lane >> 4;
-                        const int nf = slot_feature(200, t, i / 4, i % 4);
-                        const int kf = 32 * c + (c < F / 32 ? 16 * (j >> 2) + 4 * g + (j & 3) : 8 * g + j);
-                        if (nf >= 0 && kf < F) s0p[(((size_t)c * 13 + t) * 64 + lane) * 8 + j] = N::w_off(0) + nf * F + kf;
-                    }
-        // the narrow layers for chain_bf16_pair: layer l as [k block c][output tile t] fragments, lane (i, g) element j =
-        // W_l[slot (t, i / 4, i % 4) of the outputs][slot (tile 2 c + j / 4, g, j % 4) of the inputs]
-        auto chain_map = [](int l0) {
-            std::vector<int> m;
-            for (int l = l0; l < l0 + 3; ++l) {
-                const int K = N::dim(l), NN = N::dim(l + 1), kbk = (tiles(K) + 1) / 2, nt = tiles(NN);
-                const size_t off = m.size();
-                m.resize(off + (size_t)kbk * nt * 64 * 8, -1);
-                for (int c = 0; c < kbk; ++c)
-                    for (int t = 0; t < nt; ++t)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 8; ++j) {
-                                const int i = lane & 15, g = lane >> 4, q = 2 * c + j / 4;
-                                const int nf = slot_feature(NN, t, i / 4, i % 4), kf = q < tiles(K) ? slot_feature(K, q, g, j % 4) : -1;
-                                if (nf >= 0 && kf >= 0) m[off + (((size_t)c * nt + t) * 64 + lane) * 8 + j] = N::w_off(l) + nf * K + kf;
-                            }
-            }
+        // the wide side in chunks of 32 features: [chunk c][tile t of the 200 side] fragments, lane (i, g) element j = the parameter
+        // at(nf, kf) with nf = slot (t, i / 4, i % 4) of the 200 side and kf = 32 c + in_chunk(c, g, j) of the wide side
+        auto chunk_map = [](auto in_chunk, auto at) {
+            std::vector<int> m((size_t)KB * 13 * 64 * 8, -1);
+            for (int c = 0; c < KB; ++c)
+                for (int t = 0; t < 13; ++t)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            const int i = lane & 15, g = lane >> 4;
+                            const int nf = slot_feature(200, t, i / 4, i % 4), kf = 32 * c + in_chunk(c, g, j);
+                            if (nf >= 0 && kf < F) m[(((size_t)c * 13 + t) * 64 + lane) * 8 + j] = at(nf, kf);
+                        }
             return m;
         };
-        const std::vector<int> sce = chain_map(1), scd = chain_map(4);
-        const std::vector<int> *srcs[6] = {&s0, &s7, &s7t, &s0p, &sce, &scd};
+        auto natural = [](int, int g, int j) { return 8 * g + j; };
+        auto w0_at = [](int nf, int kf) { return N::w_off(0) + nf * F + kf; };
+        // layer l for chain_bf16_pair: [k block c][output tile t] fragments ([t][c] where t_major), lane (i, g) element j =
+        // W_l[slot (t, i / 4, i % 4) of the outputs][slot (tile 2 c + j / 4, g, j % 4) of the inputs]
+        auto chain_layer = [](std::vector<int> &m, int l, bool t_major) {
+            const int K = N::dim(l), NN = N::dim(l + 1), kbk = (tiles(K) + 1) / 2, nt = tiles(NN);
+            const size_t off = m.size();
+            m.resize(off + (size_t)kbk * nt * 64 * 8, -1);
+            for (int c = 0; c < kbk; ++c)
+                for (int t = 0; t < nt; ++t)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            const int i = lane & 15, g = lane >> 4, q = 2 * c + j / 4;
+                            const int nf = slot_feature(NN, t, i / 4, i % 4), kf = q < tiles(K) ? slot_feature(K, q, g, j % 4) : -1;
+                            const size_t frag = t_major ? (size_t)t * kbk + c : (size_t)c * nt + t;
+                            if (nf >= 0 && kf >= 0) m[off + (frag * 64 + lane) * 8 + j] = N::w_off(l) + nf * K + kf;
+                        }
+        };
+        std::vector<int> srcs[WB_SLOTS];
+        srcs[WB_W0] = chunk_map(natural, w0_at);
+        chain_layer(srcs[WB_W7], 7, true);
+        // W7^T for the input-gradient product of training, in en1's [chunk of 32 wide features][tile of the 200 side] order
+        srcs[WB_W7T] = chunk_map(natural, [](int nf, int kf) { return N::w_off(7) + kf * 200 + nf; });
+        // W0 once more for the DMA encode kernel: full chunks in ITS k order -- k slot (g, j) <-> feature 16 (j >> 2) + 4 g + (j & 3) of the
+        // chunk, what a lane holds after reading bytes 16 g .. + 15 of each 64-byte half of the row's chunk; a partial last chunk natural
+        srcs[WB_W0_DMA] = chunk_map([](int c, int g, int j) { return c < F / 32 ? 16 * (j >> 2) + 4 * g + (j & 3) : 8 * g + j; }, w0_at);
+        for (int l = 1; l <= 3; ++l) chain_layer(srcs[WB_CHAIN_ENC], l, false);
+        for (int l = 4; l <= 6; ++l) chain_layer(srcs[WB_CHAIN_DEC], l, false);
         if constexpr (kDma)
             BAMD_HIP(hipFuncSetAttribute((const void *)wide_bf16_encode_dma_kernel<F, Z>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dma_lds_bytes()));
         BAMD_HIP(hipFuncSetAttribute((const void *)wide_bf16_decode_kernel<F, Z, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dec_lds_bytes()));
         BAMD_HIP(hipFuncSetAttribute((const void *)wide_bf16_decode_kernel<F, Z, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dec_lds_bytes()));
-        for (int k = 0; k < 6; ++k) {
-            st->wb_count[k] = (int)srcs[k]->size();
-            rc = st->wb_src[k].ensure(srcs[k]->size() * sizeof(int));
+        for (int k = 0; k < WB_SLOTS; ++k) {
+            st->wb_count[k] = (int)srcs[k].size();
+            rc = st->wb_src[k].ensure(srcs[k].size() * sizeof(int));
             if (rc) return rc;
-            rc = st->wb[k].ensure(srcs[k]->size() * sizeof(__bf16) + 4096);
+            rc = st->wb[k].ensure(srcs[k].size() * sizeof(__bf16) + 4096);
             if (rc) return rc;
-            BAMD_HIP(hipMemcpy(st->wb_src[k].p, srcs[k]->data(), srcs[k]->size() * sizeof(int), hipMemcpyHostToDevice));
+            BAMD_HIP(hipMemcpy(st->wb_src[k].p, srcs[k].data(), srcs[k].size() * sizeof(int), hipMemcpyHostToDevice));
         }
         return BAMD_OK;
     }
     static int pack_extra(bamd_handle *h, FusedState *st, hipStream_t s) {
-        for (int k = 0; k < 6; ++k)
+        for (int k = 0; k < WB_SLOTS; ++k)
             hipLaunchKernelGGL(pack_wide_bf16_k, dim3((st->wb_count[k] + 255) / 256), dim3(256), 0, s, (const float *)h->params.p,
                                (const int *)st->wb_src[k].p, st->wb_count[k], (__bf16 *)st->wb[k].p);
         st->wb_stale = false;
@@ -4518,37 +4510,26 @@ template <int F, int Z> struct ImplWideBf16 {
                       hipStream_t s) {
         FusedState *st = state_of(h);
         if (st->wb_stale) { int rc = pack_extra(h, st, s); if (rc) return rc; }
-        const size_t xes = dtype_bytes(x_dtype), zes = dtype_bytes(z_dtype);
-        for (int64_t r0 = 0; r0 < n; r0 += W::kChunkRows) {
-            const int64_t rows = n - r0 < W::kChunkRows ? n - r0 : W::kChunkRows;
-            const void *src = (const char *)x + (size_t)r0 * F * xes;
-            int src_f64 = x_dtype == BAMD_F64;
-            if (features) {
-                int rc = h->work.ensure((size_t)rows * F * sizeof(float));
-                if (rc) return rc;
-                rc = launch_normalize(src, x_dtype, rows, F, features, h->work.p, BAMD_F32, s);
-                if (rc) return rc;
-                src = h->work.p;
-                src_f64 = 0;
-            }
+        const size_t zes = dtype_bytes(z_dtype);
+        const int rc = wide_in_chunks(h, x, x_dtype, n, F, features, kChunkRows, false, s, [&](const void *src, int src_f64, int64_t rows, int64_t r0) -> int {
             const int64_t ngroup = (rows + 127) / 128;
             const dim3 grid((unsigned)(ngroup > 2048 ? 2048 : ngroup));
             void *zo = (void *)((char *)z + (size_t)r0 * Z * zes);
             if constexpr (kDma) {
                 if (!src_f64) {      // persistent: one workgroup (4 compute + 2 loader waves, 150 KiB of LDS) per CU
                     hipLaunchKernelGGL((wide_bf16_encode_dma_kernel<F, Z>), dim3((unsigned)(ngroup > st->nwg_max ? st->nwg_max : ngroup)), dim3(384),
-                                       dma_lds_bytes(), s, (const v4 *)h->packed.p, (const v4 *)st->wb[3].p, (const v4 *)st->wb[4].p, (const float *)src, rows, zo,
-                                       z_dtype == BAMD_F64);
-                    continue;
+                                       dma_lds_bytes(), s, (const v4 *)h->packed.p, (const v4 *)st->wb[WB_W0_DMA].p, (const v4 *)st->wb[WB_CHAIN_ENC].p,
+                                       (const float *)src, rows, zo, z_dtype == BAMD_F64);
+                    return BAMD_OK;
                 }
             }
-            if (src_f64)
-                hipLaunchKernelGGL((wide_bf16_encode_kernel<F, Z, true>), grid, dim3(256), 0, s, (const v4 *)h->packed.p,
-                                   (const v4 *)st->wb[0].p, src, rows, zo, z_dtype == BAMD_F64);
-            else
-                hipLaunchKernelGGL((wide_bf16_encode_kernel<F, Z, false>), grid, dim3(256), 0, s, (const v4 *)h->packed.p,
-                                   (const v4 *)st->wb[0].p, src, rows, zo, z_dtype == BAMD_F64);
-        }
+            with_bool(src_f64, [&](auto in64) {
+                hipLaunchKernelGGL((wide_bf16_encode_kernel<F, Z, decltype(in64)::value>), grid, dim3(256), 0, s, (const v4 *)h->packed.p,
+                                   (const v4 *)st->wb[WB_W0].p, src, rows, zo, z_dtype == BAMD_F64);
+            });
+            return BAMD_OK;
+        });
+        if (rc) return rc;
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
@@ -4556,32 +4537,12 @@ template <int F, int Z> struct ImplWideBf16 {
                       void *out, int out_dtype, hipStream_t s) {
         FusedState *st = state_of(h);
         if (st->wb_stale) { int rc = pack_extra(h, st, s); if (rc) return rc; }
-        const size_t zes = dtype_bytes(z_dtype), oes = dtype_bytes(out_dtype);
-        if (features && out_dtype != BAMD_F64) { set_error("decode with features needs a float64 output"); return BAMD_ERR_INVALID; }
-        for (int64_t r0 = 0; r0 < n; r0 += W::kChunkRows) {
-            const int64_t rows = n - r0 < W::kChunkRows ? n - r0 : W::kChunkRows;
-            void *dst = (char *)out + (size_t)r0 * F * oes;
-            void *kout = dst;
-            int kout_f64 = out_dtype == BAMD_F64;
-            if (features) {
-                int rc = h->work.ensure((size_t)rows * F * sizeof(float));
-                if (rc) return rc;
-                kout = h->work.p;
-                kout_f64 = 0;
-            }
-            if (kout_f64)
-                hipLaunchKernelGGL((wide_bf16_decode_kernel<F, Z, true>), dim3(dec_grid(st, rows)), dim3(320), dec_lds_bytes(), s, (const v4 *)h->packed.p,
-                                   (const v4 *)st->wb[1].p, (const v4 *)st->wb[5].p, (const void *)((const char *)z + (size_t)r0 * Z * zes), z_dtype == BAMD_F64, rows, kout);
-            else
-                hipLaunchKernelGGL((wide_bf16_decode_kernel<F, Z, false>), dim3(dec_grid(st, rows)), dim3(320), dec_lds_bytes(), s, (const v4 *)h->packed.p,
-                                   (const v4 *)st->wb[1].p, (const v4 *)st->wb[5].p, (const void *)((const char *)z + (size_t)r0 * Z * zes), z_dtype == BAMD_F64, rows, kout);
-            if (features) {
-                int rc = launch_renormalize(kout, BAMD_F32, rows, F, features, int_mask, (double *)dst, s);
-                if (rc) return rc;
-            }
-        }
-        BAMD_HIP(hipGetLastError());
-        return BAMD_OK;
+        return wide_out_chunks(h, z, z_dtype, Z, n, F, features, int_mask, out, out_dtype, s, [&](const void *zi, int64_t rows, void *kout, bool kout_f64) {
+            with_bool(kout_f64, [&](auto out64) {
+                hipLaunchKernelGGL((wide_bf16_decode_kernel<F, Z, decltype(out64)::value>), dim3(dec_grid(st, rows)), dim3(320), dec_lds_bytes(), s,
+                                   (const v4 *)h->packed.p, (const v4 *)st->wb[WB_W7].p, (const v4 *)st->wb[WB_CHAIN_DEC].p, zi, z_dtype == BAMD_F64, rows, kout);
+            });
+        });
     }
     // training: the row-local launches with en1 / de4 / de4's input-gradient product on the bf16 MFMA (BALER_AMD_BF16_WIDE_TRAIN=0: the
     // float32 launches, as before round 3); the weight-gradient products stay in float32 on what these launches store
@@ -4596,18 +4557,13 @@ template <int F, int Z> struct ImplWideBf16 {
         FusedState *st = state_of(h);
         if (st->wb_stale) { int rc = pack_extra(h, st, s); if (rc) return rc; }
         const int grid = grid_for(rows);
-        if constexpr (F % 4 == 0) {
-            if (st->dz16) {
-                hipLaunchKernelGGL((wide_bf16_train_fwd_kernel<F, Z, true>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p,
-                                   (const v4 *)st->wb[0].p, (const v4 *)st->wb[1].p, x, rows, y[1], y[2], y[3], y[4], y[5], y[6], y[7],
+        with_bool(F % 4 == 0 && st->dz16, [&](auto dz16) {
+            constexpr bool DZ16 = decltype(dz16)::value;
+            if constexpr (!DZ16 || F % 4 == 0)
+                hipLaunchKernelGGL((wide_bf16_train_fwd_kernel<F, Z, DZ16>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p,
+                                   (const v4 *)st->wb[WB_W0].p, (const v4 *)st->wb[WB_W7].p, x, rows, y[1], y[2], y[3], y[4], y[5], y[6], y[7],
                                    (void *)dz_last, loss_part);
-                *nblk = grid;
-                BAMD_HIP(hipGetLastError());
-                return BAMD_OK;
-            }
-        }
-        hipLaunchKernelGGL((wide_bf16_train_fwd_kernel<F, Z, false>), dim3(grid), dim3(256), 0, s, (const v4 *)h->packed.p, (const v4 *)st->wb[0].p,
-                           (const v4 *)st->wb[1].p, x, rows, y[1], y[2], y[3], y[4], y[5], y[6], y[7], (void *)dz_last, loss_part);
+        });
         *nblk = grid;
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
@@ -4616,20 +4572,14 @@ template <int F, int Z> struct ImplWideBf16 {
         if (!bf16_train_on() || W::small_pass(h, rows)) return W::wide_bwd(h, rows, y, dz, dz_latent, s);
         FusedState *st = state_of(h);
         if (st->wb_stale) { int rc = pack_extra(h, st, s); if (rc) return rc; }
-        if constexpr (F % 4 == 0) {
-            if (st->dz16) {
-                hipLaunchKernelGGL((wide_bf16_train_bwd_kernel<F, Z, true>), dim3(grid_for(rows)), dim3(256), 0, s, (const v4 *)h->packed.p,
-                                   (const v4 *)st->wb[2].p, (const void *)dz[7], rows, (const float *)y[1], (const float *)y[2],
+        with_bool(F % 4 == 0 && st->dz16, [&](auto dz16) {
+            constexpr bool DZ16 = decltype(dz16)::value;
+            if constexpr (!DZ16 || F % 4 == 0)
+                hipLaunchKernelGGL((wide_bf16_train_bwd_kernel<F, Z, DZ16>), dim3(grid_for(rows)), dim3(256), 0, s, (const v4 *)h->packed.p,
+                                   (const v4 *)st->wb[WB_W7T].p, (const void *)dz[7], rows, (const float *)y[1], (const float *)y[2],
                                    (const float *)y[3], (const float *)y[5], (const float *)y[6], (const float *)y[7], dz[0], dz[1], dz[2],
                                    dz[3], dz[4], dz[5], dz[6], dz_latent);
-                BAMD_HIP(hipGetLastError());
-                return BAMD_OK;
-            }
-        }
-        hipLaunchKernelGGL((wide_bf16_train_bwd_kernel<F, Z, false>), dim3(grid_for(rows)), dim3(256), 0, s, (const v4 *)h->packed.p,
-                           (const v4 *)st->wb[2].p, (const void *)dz[7], rows, (const float *)y[1], (const float *)y[2], (const float *)y[3],
-                           (const float *)y[5], (const float *)y[6], (const float *)y[7], dz[0], dz[1], dz[2], dz[3], dz[4], dz[5], dz[6],
-                           dz_latent);
+        });
         BAMD_HIP(hipGetLastError());
         return BAMD_OK;
     }
@@ -4782,7 +4732,7 @@ static void release_state(FusedState *st) {
     st->imgs.release();
     st->dwpart.release();
     st->wpart.release();
-    for (int k = 0; k < 6; ++k) { st->wb_src[k].release(); st->wb[k].release(); }
+    for (int k = 0; k < WB_SLOTS; ++k) { st->wb_src[k].release(); st->wb[k].release(); }
     st->sc_off.release();
     st->sc_idx.release();
     delete st;

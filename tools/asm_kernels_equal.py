@@ -15,7 +15,7 @@ import sys
 
 BEGIN = re.compile(r"^\t\.section\t\.text\.([A-Za-z0-9_$.]+),")
 LABEL = re.compile(r"\.L(BB|JTI|CPI|tmp)\d+_|\.Lfunc_(begin|end)\d+")
-LOOP = re.compile(r"(Header=|Child Loop )BB\d+_")      # the same index in the loop comments
+LOOP = re.compile(r"(Header=|Child Loop |Parent Loop )BB\d+_")      # the same index in the loop comments
 
 
 def unnumber(line):      # ... and the padding in front of a comment, which follows the label's width
