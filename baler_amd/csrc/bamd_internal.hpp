@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/baler_amd.h"
@@ -50,6 +51,11 @@ inline long long env_ll(const char *name, long long dflt) {
 inline bool env_off(const char *name) {      // "NAME=0" switches a default-on path off
     const char *e = getenv(name);
     return e && e[0] == '0';
+}
+// a run-time bool as a template argument: fn(std::true_type / std::false_type)
+template <class Fn> inline void with_bool(bool b, Fn &&fn) {
+    if (b) fn(std::true_type{});
+    else fn(std::false_type{});
 }
 
 struct DevBuf {

@@ -3910,12 +3910,6 @@ struct FusedOps {
 
 static FusedState *state_of(bamd_handle *h) { return (FusedState *)h->fused_state; }
 
-// a run-time bool as a template argument: fn(std::true_type / std::false_type)
-template <class Fn> static void with_bool(bool b, Fn &&fn) {
-    if (b) fn(std::true_type{});
-    else fn(std::false_type{});
-}
-
 // Does Net<F, Z> serve this handle?  An exact instantiation: all nine widths.  A class (run-time widths): the hidden widths, and
 // f_min .. F columns with a latent of z_min .. Z.
 template <int F, int Z> static bool net_matches(const bamd_handle *h, bool cls, int f_min, int z_min) {

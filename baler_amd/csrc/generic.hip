@@ -437,93 +437,59 @@ static void launch_gemm(const Opnd<T> &A, const Opnd<T> &B, int64_t kred, const 
 // the P loads through the L1; operands of the next 16-row block are loaded while the current block multiplies (two register
 // sets, no copies).  P_IS_N: P = dZ (n side), Q = [X | 1]; otherwise P = [X | 1], Q = dZ.  The ones column is a select on the
 // tile that holds column K.  Output: this split's slab [n * K + k | n] (fixed order reduction by reduce_layers_k).
-template <int PT, int TQ, bool P_IS_N>
-__global__ void __launch_bounds__(256) dw_short_k(const float *__restrict__ dzm, const float *__restrict__ xm, int N, int K, int64_t rows,
-                                                  int64_t rps, float *__restrict__ slab, int64_t slab_size) {
-    using v4 = MF<float>::v4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+//
+// Four kernels: {plain 16-column tiles, strided tiles with 16-byte loads} x {fp32 MFMA on 16-row blocks, bf16 MFMA on 32-row blocks}.
+// What they share is written once, here; a kernel keeps its column-to-lane map (per-lane offsets, ones-column predicates), its operand
+// structs and the bodies of its `load` / `mma` (/ `pack`).
+typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+typedef unsigned u4 __attribute__((ext_vector_type(4)));
+typedef unsigned u2 __attribute__((ext_vector_type(2)));
+
+// The split: which matrix is P and which Q, their widths, this workgroup's row range.  Operand loads go through buffer resources based at
+// the split's first row: ONE byte offset per lane and operand side in a VGPR, block and step offsets in SGPRs -- no 64-bit address
+// arithmetic on the vector unit (global loads cost one v_lshl_add_u64 each).  The host keeps rows-per-split x width below 2^29 elements.
+struct DwSplit {
+    int DP, DQ;                        // stored widths
+    int CQ;                            // logical columns of Q
+    int64_t nr;                        // rows of the split
+    __amdgpu_buffer_rsrc_t rp, rq;
+};
+// q_col0: the wave's first Q column; qes: bytes per stored element of Q (2: dZ stored as bfloat16).  false: nothing to do (the wave's Q
+// columns are beyond CQ, or the split has no rows).  Two exits, in this order: folded into one test they compile to one merged branch, and
+// dw_wide_k<false> spills 32 bytes more.
+template <bool P_IS_N>
+__device__ __forceinline__ bool dw_split(DwSplit &s, const float *__restrict__ dzm, const float *__restrict__ xm, int N, int K, int64_t rows,
+                                         int64_t rps, int q_col0, int qes = 4) {
     const float *__restrict__ pm = P_IS_N ? dzm : xm;
     const float *__restrict__ qm = P_IS_N ? xm : dzm;
-    const int DP = P_IS_N ? N : K, DQ = P_IS_N ? K : N;            // stored widths
-    const int CQ = P_IS_N ? K + 1 : N;                             // logical columns of Q
-    const int qt0 = ((int)blockIdx.x * 4 + wave) * TQ;
-    if (qt0 * 16 >= CQ) return;
+    s.DP = P_IS_N ? N : K;
+    s.DQ = P_IS_N ? K : N;
+    s.CQ = P_IS_N ? K + 1 : N;
+    if (q_col0 >= s.CQ) return false;
     const int64_t r_begin = (int64_t)blockIdx.y * rps;
     const int64_t r_end = r_begin + rps < rows ? r_begin + rps : rows;
-    if (r_begin >= r_end) return;
-    // per-lane element offsets inside a 16-row block (columns beyond the stored width re-read the last column: their
-    // accumulators are padding and never stored)
-    // Operand loads go through buffer resources based at the split's first row: ONE byte offset per lane and operand side in a
-    // VGPR (tile t = +64 t bytes, an immediate; PT = tiles(logical columns), so only the LAST P tile can reach beyond the stored
-    // width and has its own clamped offset), block and step offsets in SGPRs -- no 64-bit address arithmetic on the vector unit
-    // (global loads cost one v_lshl_add_u64 each).  The host keeps rows-per-split x width below 2^29 elements.
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void *)(pm + r_begin * DP), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)(qm + r_begin * DQ), 0, 0x7fffffff, 0x00020000);
-    int offq[TQ];
-    const int offp0 = (g * DP + i) * 4;
-    const int offpl = (g * DP + (16 * (PT - 1) + i < DP ? 16 * (PT - 1) + i : DP - 1)) * 4;
-#pragma unroll
-    for (int u = 0; u < TQ; ++u) { const int c = 16 * (qt0 + u) + i; offq[u] = (g * DQ + (c < DQ ? c : DQ - 1)) * 4; }
-    auto ldp = [&](int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, voff, soff, 0)); };
-    auto ldq = [&](int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rq, voff, soff, 0)); };
-    const bool p_one = !P_IS_N && 16 * (PT - 1) + i == K;          // this lane's column of the LAST P tile is the ones column
-    bool q_one[TQ];
-#pragma unroll
-    for (int u = 0; u < TQ; ++u) q_one[u] = P_IS_N && 16 * (qt0 + u) + i == K;
-    v4 acc[TQ][PT];
-#pragma unroll
-    for (int u = 0; u < TQ; ++u)
-#pragma unroll
-        for (int t = 0; t < PT; ++t) acc[u][t] = (v4){0.f, 0.f, 0.f, 0.f};
-    struct Frags { v4 p[PT]; v4 q[TQ]; };
-    auto load = [&](Frags &f, int64_t rb, bool tail) {      // rb = first row of the block, relative to r_begin
-        const int sp = (int)rb * DP * 4, sq = (int)rb * DQ * 4;
-        if (!tail) {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-#pragma unroll
-                for (int u = 0; u < TQ; ++u) f.q[u][s4] = ldq(offq[u], sq + s4 * 16 * DQ);
-#pragma unroll
-                for (int t = 0; t < PT; ++t) f.p[t][s4] = ldp(t == PT - 1 ? offpl : offp0 + 64 * t, sp + s4 * 16 * DP);
-            }
-        } else {            // last block of the range: rows beyond it read the last row and contribute zero through dZ
-            const int64_t nr = r_end - r_begin;
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const bool ok = rb + 4 * s4 + g < nr;
-                const int back = ok ? 0 : (int)(rb + 4 * s4 + g - (nr - 1));
-#pragma unroll
-                for (int u = 0; u < TQ; ++u) {
-                    const float v = ldq(offq[u] - back * DQ * 4, sq + s4 * 16 * DQ);
-                    f.q[u][s4] = (!P_IS_N && !ok) ? 0.f : v;
-                }
-#pragma unroll
-                for (int t = 0; t < PT; ++t) {
-                    const float v = ldp((t == PT - 1 ? offpl : offp0 + 64 * t) - back * DP * 4, sp + s4 * 16 * DP);
-                    f.p[t][s4] = (P_IS_N && !ok) ? 0.f : v;
-                }
-            }
-        }
-    };
-    auto mma = [&](Frags &f) {
-        if (!P_IS_N) {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) f.p[PT - 1][s4] = p_one ? 1.0f : f.p[PT - 1][s4];
-        } else {
-#pragma unroll
-            for (int u = 0; u < TQ; ++u)
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) f.q[u][s4] = q_one[u] ? 1.0f : f.q[u][s4];
-        }
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-            for (int u = 0; u < TQ; ++u)
-#pragma unroll
-                for (int t = 0; t < PT; ++t) acc[u][t] = MF<float>::mma(f.q[u][s4], f.p[t][s4], acc[u][t]);
-    };
-    Frags fa, fb;
-    const int64_t nfull = (r_end - r_begin) >> 4;          // full 16-row blocks; the loop below never sees the ragged one
+    if (r_begin >= r_end) return false;
+    s.nr = r_end - r_begin;
+    s.rp = __builtin_amdgcn_make_buffer_rsrc((void *)(pm + r_begin * s.DP), 0, 0x7fffffff, 0x00020000);
+    s.rq = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)qm + r_begin * s.DQ * qes), 0, 0x7fffffff, 0x00020000);
+    return true;
+}
+
+// The ragged last block of a split: a row beyond the range re-reads the range's last row (`back` rows up) and contributes zero through
+// dZ, which the caller zeroes where !ok.  rb: the block's first row; row: the lane's row inside the block (4 s + g in fp32, 8 g + e in bf16).
+struct DwTail { bool ok; int back; };
+__device__ __forceinline__ DwTail dw_tail(int64_t rb, int row, int64_t nr) {
+    const bool ok = rb + row < nr;
+    return {ok, ok ? 0 : (int)(rb + row - (nr - 1))};
+}
+
+// fp32 row pipeline: operands of the next 16-row block are loaded while the current block multiplies (two register sets, no copies).
+// load(f, first row of the block, tail); mma(f).  The loop never sees the ragged block.  The two sets are the kernel's own locals: declared
+// here they would carry lifetime markers into the kernel, and dw_wide_k, which has no register to spare, then spills 16 bytes more.
+template <class Frags, class Load, class Mma>
+__device__ __forceinline__ void dw_rows_f32(int64_t nr, Frags &fa, Frags &fb, Load &&load, Mma &&mma) {
+    const int64_t nfull = nr >> 4;
     if (nfull > 0) {
         load(fa, 0, false);
         int64_t b = 0;
@@ -545,12 +511,51 @@ __global__ void __launch_bounds__(256) dw_short_k(const float *__restrict__ dzm,
             mma(fa);
         }
     }
-    if ((r_end - r_begin) & 15) {
+    if (nr & 15) {
         load(fa, 16 * nfull, true);
         mma(fa);
     }
-    // C map: register r of lane (g, i) = (q column 4 g + r of the tile, p column i)
-    float *out = slab + (int64_t)blockIdx.y * slab_size;
+}
+
+// bf16 row pipeline over 32-row blocks: load(raw, first row, tail); pack(pk, raw) rounds to bfloat16 in MFMA layout; mma(pk).
+template <class Raw, class Pk, class Load, class Pack, class Mma>
+__device__ __forceinline__ void dw_rows_bf16(int64_t nr, Raw &ra, Pk &pk, Load &&load, Pack &&pack, Mma &&mma) {
+    const int64_t nfull = nr >> 5;
+    if (nfull > 0) {
+        load(ra, 0, false);
+        for (int64_t b = 0; b < nfull; ++b) {
+            pack(pk, ra);
+            __builtin_amdgcn_sched_barrier(0);
+            if (b + 1 < nfull) load(ra, 32 * (b + 1), false);      // the next block's rows stream in behind this block's MFMAs
+            __builtin_amdgcn_sched_barrier(0);
+            mma(pk);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (nr & 31) {
+        load(ra, 32 * nfull, true);
+        pack(pk, ra);
+        mma(pk);
+    }
+}
+
+// at(0) .. at(7), eight floats, to the eight k slots of one bf16 MFMA operand: four v_cvt_pk_bf16_f32
+template <class At> __device__ __forceinline__ bf8 pack8(At &&at) {
+    const bf2 p0 = {(__bf16)at(0), (__bf16)at(1)}, p1 = {(__bf16)at(2), (__bf16)at(3)}, p2 = {(__bf16)at(4), (__bf16)at(5)}, p3 = {(__bf16)at(6), (__bf16)at(7)};
+    const u4 w = {__builtin_bit_cast(unsigned, p0), __builtin_bit_cast(unsigned, p1), __builtin_bit_cast(unsigned, p2),
+                  __builtin_bit_cast(unsigned, p3)};
+    return __builtin_bit_cast(bf8, w);
+}
+
+// Plain-tile epilogue.  C map: register r of lane (g, i) in accumulator (u, t) = (q column 16 (qt0 + u) + 4 g + r, p column 16 t + i).
+// The 16-byte store needs K % 4 == 0.  dw_short_bf16_k never takes it, so the test costs it a compare and stores the same.  That rests on two
+// rules: run_dw_short launches it only for a chunk with ChunkRoute::bf16_ops, i.e. a fused_wide_train model, whose P-is-N layer of 13 tiles has
+// N = 200 (its hidden width: N % 4 == 0, N >= 192); and plan_short_dw's `wide` gives such a layer with K % 4 == 0 to dw_wide_bf16_k.  What is
+// left for dw_short_bf16_k<13, 2, true> has K % 4 != 0.  A change to either rule can make the path live there: it stores the same values
+// (as in dw_short_k), at addresses that are 16-byte aligned only where the split's slab is.
+template <int PT, int TQ, bool P_IS_N>
+__device__ __forceinline__ void dw_store_plain(const MF<float>::v4 (&acc)[TQ][PT], float *out, int qt0, int g, int i, int N, int K) {
+    using v4 = MF<float>::v4;
 #pragma unroll
     for (int u = 0; u < TQ; ++u) {
         const int q0 = 16 * (qt0 + u) + 4 * g;
@@ -582,121 +587,11 @@ __global__ void __launch_bounds__(256) dw_short_k(const float *__restrict__ dzm,
     }
 }
 
-// The two WIDE weight gradients of a wide model (200 x 2501, 2500 x 201): the same structure with 16-byte operand loads.  The
-// vector-memory pipe issues one wave instruction per ~16 cycles whatever its width, so dword operand loads (60 per 104 MFMAs and
-// wave above) make the four waves of a CU VMEM-issue bound (measured: MFMA busy 45 %, 8 % of the cycles in s_waitcnt).  Here lane
-// (g, i) loads FOUR consecutive columns 4 i .. 4 i + 3 of row 4 s + g: register j of that load is the step-s operand of the
-// "strided tile" {64 G + 4 i + j : i = 0..15} of column group G -- a legal MFMA operand, since the column-to-lane map of an
-// operand is free as long as the epilogue knows it.  The short side (193..208 logical columns) is 3 groups (12 strided tiles) +
-// 1 plain tile of dword loads, the other side one group per wave: 20 loads per 208 MFMAs.  52 accumulator tiles (AGPRs), two
-// operand sets of 68 registers.  Needs widths and K divisible by 4 (16-byte rows; the ones column starts a 4-column group).
+// Strided-tile epilogue.  C map: register r of lane (g, i) in accumulator (u, t): Q column 64 gq + 16 g + 4 r + u; P column
+// 64 G + 4 i + j for the strided tile t = 4 G + j, 192 + i for the plain tile t = 12.
 template <bool P_IS_N>
-__global__ void __launch_bounds__(256) dw_wide_k(const float *__restrict__ dzm, const float *__restrict__ xm, int N, int K, int64_t rows,
-                                                 int64_t rps, float *__restrict__ slab, int64_t slab_size) {
+__device__ __forceinline__ void dw_store_strided(const MF<float>::v4 (&acc)[4][13], float *out, int gq, int g, int i, int N, int K) {
     using v4 = MF<float>::v4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
-    const float *__restrict__ pm = P_IS_N ? dzm : xm;
-    const float *__restrict__ qm = P_IS_N ? xm : dzm;
-    const int DP = P_IS_N ? N : K, DQ = P_IS_N ? K : N;
-    const int CQ = P_IS_N ? K + 1 : N;
-    const int gq = (int)blockIdx.x * 4 + wave;                     // this wave's column group of Q
-    if (64 * gq >= CQ) return;
-    const int64_t r_begin = (int64_t)blockIdx.y * rps;
-    const int64_t r_end = r_begin + rps < rows ? r_begin + rps : rows;
-    if (r_begin >= r_end) return;
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void *)(pm + r_begin * DP), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)(qm + r_begin * DQ), 0, 0x7fffffff, 0x00020000);
-    // columns beyond the stored width re-read the last 4 columns (padding accumulators, never stored)
-    const int cq = 64 * gq + 4 * i;
-    const int offq = (g * DQ + (cq + 4 <= DQ ? cq : DQ - 4)) * 4;
-    const int offpg = (g * DP + 4 * i) * 4;                                       // group G: + 256 G bytes
-    const int offpl = (g * DP + (192 + i < DP ? 192 + i : DP - 1)) * 4;           // the plain tile: columns 192 + i
-    const bool q_one = P_IS_N && cq == K;            // register 0 of this lane's Q load is the ones column
-    const bool p_one = !P_IS_N && 192 + i == K;
-    auto ld4 = [&](const __amdgpu_buffer_rsrc_t &r, int voff, int soff) {
-        return __builtin_bit_cast(v4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    v4 acc[4][13];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int t = 0; t < 13; ++t) acc[u][t] = (v4){0.f, 0.f, 0.f, 0.f};
-    struct Frags { v4 pg[3][4]; v4 pl; v4 q[4]; };                 // [group][step], plain tile [step], [step]
-    auto load = [&](Frags &f, int64_t rb, bool tail) {
-        const int sp = (int)rb * DP * 4, sq = (int)rb * DQ * 4;
-        const int64_t nr = r_end - r_begin;
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            int back_p = 0, back_q = 0;
-            bool ok = true;
-            if (tail) {                                            // rows beyond the range read its last row, dZ zeroed
-                ok = rb + 4 * s4 + g < nr;
-                const int back = ok ? 0 : (int)(rb + 4 * s4 + g - (nr - 1));
-                back_p = back * DP * 4;
-                back_q = back * DQ * 4;
-            }
-            f.q[s4] = ld4(rq, offq - back_q, sq + s4 * 16 * DQ);
-#pragma unroll
-            for (int G = 0; G < 3; ++G) f.pg[G][s4] = ld4(rp, offpg + 256 * G - back_p, sp + s4 * 16 * DP);
-            f.pl[s4] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, offpl - back_p, sp + s4 * 16 * DP, 0));
-            if (tail && !ok) {
-                if (P_IS_N) {
-#pragma unroll
-                    for (int G = 0; G < 3; ++G) f.pg[G][s4] = (v4){0.f, 0.f, 0.f, 0.f};
-                    f.pl[s4] = 0.f;
-                } else {
-                    f.q[s4] = (v4){0.f, 0.f, 0.f, 0.f};
-                }
-            }
-        }
-    };
-    auto mma = [&](Frags &f) {
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            if (P_IS_N) f.q[s4][0] = q_one ? 1.0f : f.q[s4][0];
-            else f.pl[s4] = p_one ? 1.0f : f.pl[s4];
-        }
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                for (int G = 0; G < 3; ++G)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[u][4 * G + j] = MF<float>::mma(f.q[s4][u], f.pg[G][s4][j], acc[u][4 * G + j]);
-                acc[u][12] = MF<float>::mma(f.q[s4][u], f.pl[s4], acc[u][12]);
-            }
-    };
-    Frags fa, fb;
-    const int64_t nfull = (r_end - r_begin) >> 4;
-    if (nfull > 0) {
-        load(fa, 0, false);
-        int64_t b = 0;
-        for (; b + 2 < nfull; b += 2) {
-            load(fb, 16 * (b + 1), false);          // issue the next block's loads BEFORE this block's MFMAs (hipcc sinks them otherwise)
-            __builtin_amdgcn_sched_barrier(0);
-            mma(fa);
-            __builtin_amdgcn_sched_barrier(0);
-            load(fa, 16 * (b + 2), false);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(fb);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (b + 2 == nfull) {
-            load(fb, 16 * (b + 1), false);
-            mma(fa);
-            mma(fb);
-        } else {
-            mma(fa);
-        }
-    }
-    if ((r_end - r_begin) & 15) {
-        load(fa, 16 * nfull, true);
-        mma(fa);
-    }
-    // C map: register r of lane (g, i) in accumulator (u, t): Q column 64 gq + 16 g + 4 r + u; P column 64 G + 4 i + j for the
-    // strided tile t = 4 G + j, 192 + i for the plain tile t = 12
-    float *out = slab + (int64_t)blockIdx.y * slab_size;
     if (P_IS_N) {                  // n = P column, k = Q column: the four Q tiles of a register are 4 consecutive k
 #pragma unroll
         for (int t = 0; t < 13; ++t) {
@@ -733,6 +628,160 @@ __global__ void __launch_bounds__(256) dw_wide_k(const float *__restrict__ dzm, 
     }
 }
 
+template <int PT, int TQ, bool P_IS_N>
+__global__ void __launch_bounds__(256) dw_short_k(const float *__restrict__ dzm, const float *__restrict__ xm, int N, int K, int64_t rows,
+                                                  int64_t rps, float *__restrict__ slab, int64_t slab_size) {
+    using v4 = MF<float>::v4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+    const int qt0 = ((int)blockIdx.x * 4 + wave) * TQ;
+    DwSplit S;
+    if (!dw_split<P_IS_N>(S, dzm, xm, N, K, rows, rps, 16 * qt0)) return;
+    const int DP = S.DP, DQ = S.DQ;
+    // per-lane byte offsets inside a 16-row block (columns beyond the stored width re-read the last column: their accumulators are
+    // padding and never stored).  Tile t = +64 t bytes, an immediate; PT = tiles(logical columns), so only the LAST P tile can reach
+    // beyond the stored width and has its own clamped offset.
+    int offq[TQ];
+    const int offp0 = (g * DP + i) * 4;
+    const int offpl = (g * DP + (16 * (PT - 1) + i < DP ? 16 * (PT - 1) + i : DP - 1)) * 4;
+#pragma unroll
+    for (int u = 0; u < TQ; ++u) { const int c = 16 * (qt0 + u) + i; offq[u] = (g * DQ + (c < DQ ? c : DQ - 1)) * 4; }
+    auto ldp = [&](int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(S.rp, voff, soff, 0)); };
+    auto ldq = [&](int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(S.rq, voff, soff, 0)); };
+    const bool p_one = !P_IS_N && 16 * (PT - 1) + i == K;          // this lane's column of the LAST P tile is the ones column
+    bool q_one[TQ];
+#pragma unroll
+    for (int u = 0; u < TQ; ++u) q_one[u] = P_IS_N && 16 * (qt0 + u) + i == K;
+    v4 acc[TQ][PT];
+#pragma unroll
+    for (int u = 0; u < TQ; ++u)
+#pragma unroll
+        for (int t = 0; t < PT; ++t) acc[u][t] = (v4){0.f, 0.f, 0.f, 0.f};
+    struct Frags { v4 p[PT]; v4 q[TQ]; };
+    auto load = [&](Frags &f, int64_t rb, bool tail) {      // rb = first row of the block, relative to r_begin
+        const int sp = (int)rb * DP * 4, sq = (int)rb * DQ * 4;
+        if (!tail) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+#pragma unroll
+                for (int u = 0; u < TQ; ++u) f.q[u][s4] = ldq(offq[u], sq + s4 * 16 * DQ);
+#pragma unroll
+                for (int t = 0; t < PT; ++t) f.p[t][s4] = ldp(t == PT - 1 ? offpl : offp0 + 64 * t, sp + s4 * 16 * DP);
+            }
+        } else {            // last block of the range
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                const DwTail tl = dw_tail(rb, 4 * s4 + g, S.nr);
+#pragma unroll
+                for (int u = 0; u < TQ; ++u) {
+                    const float v = ldq(offq[u] - tl.back * DQ * 4, sq + s4 * 16 * DQ);
+                    f.q[u][s4] = (!P_IS_N && !tl.ok) ? 0.f : v;
+                }
+#pragma unroll
+                for (int t = 0; t < PT; ++t) {
+                    const float v = ldp((t == PT - 1 ? offpl : offp0 + 64 * t) - tl.back * DP * 4, sp + s4 * 16 * DP);
+                    f.p[t][s4] = (P_IS_N && !tl.ok) ? 0.f : v;
+                }
+            }
+        }
+    };
+    auto mma = [&](Frags &f) {
+        if (!P_IS_N) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) f.p[PT - 1][s4] = p_one ? 1.0f : f.p[PT - 1][s4];
+        } else {
+#pragma unroll
+            for (int u = 0; u < TQ; ++u)
+#pragma unroll
+                for (int s4 = 0; s4 < 4; ++s4) f.q[u][s4] = q_one[u] ? 1.0f : f.q[u][s4];
+        }
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+            for (int u = 0; u < TQ; ++u)
+#pragma unroll
+                for (int t = 0; t < PT; ++t) acc[u][t] = MF<float>::mma(f.q[u][s4], f.p[t][s4], acc[u][t]);
+    };
+    Frags fa, fb;
+    dw_rows_f32(S.nr, fa, fb, load, mma);
+    dw_store_plain<PT, TQ, P_IS_N>(acc, slab + (int64_t)blockIdx.y * slab_size, qt0, g, i, N, K);
+}
+
+// The two WIDE weight gradients of a wide model (200 x 2501, 2500 x 201): the same structure with 16-byte operand loads.  The
+// vector-memory pipe issues one wave instruction per ~16 cycles whatever its width, so dword operand loads (60 per 104 MFMAs and
+// wave above) make the four waves of a CU VMEM-issue bound (measured: MFMA busy 45 %, 8 % of the cycles in s_waitcnt).  Here lane
+// (g, i) loads FOUR consecutive columns 4 i .. 4 i + 3 of row 4 s + g: register j of that load is the step-s operand of the
+// "strided tile" {64 G + 4 i + j : i = 0..15} of column group G -- a legal MFMA operand, since the column-to-lane map of an
+// operand is free as long as the epilogue knows it.  The short side (193..208 logical columns) is 3 groups (12 strided tiles) +
+// 1 plain tile of dword loads, the other side one group per wave: 20 loads per 208 MFMAs.  52 accumulator tiles (AGPRs), two
+// operand sets of 68 registers.  Needs widths and K divisible by 4 (16-byte rows; the ones column starts a 4-column group).
+template <bool P_IS_N>
+__global__ void __launch_bounds__(256) dw_wide_k(const float *__restrict__ dzm, const float *__restrict__ xm, int N, int K, int64_t rows,
+                                                 int64_t rps, float *__restrict__ slab, int64_t slab_size) {
+    using v4 = MF<float>::v4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+    const int gq = (int)blockIdx.x * 4 + wave;                     // this wave's column group of Q
+    DwSplit S;
+    if (!dw_split<P_IS_N>(S, dzm, xm, N, K, rows, rps, 64 * gq)) return;
+    const int DP = S.DP, DQ = S.DQ;
+    // columns beyond the stored width re-read the last 4 columns (padding accumulators, never stored)
+    const int cq = 64 * gq + 4 * i;
+    const int offq = (g * DQ + (cq + 4 <= DQ ? cq : DQ - 4)) * 4;
+    const int offpg = (g * DP + 4 * i) * 4;                                       // group G: + 256 G bytes
+    const int offpl = (g * DP + (192 + i < DP ? 192 + i : DP - 1)) * 4;           // the plain tile: columns 192 + i
+    const bool q_one = P_IS_N && cq == K;            // register 0 of this lane's Q load is the ones column
+    const bool p_one = !P_IS_N && 192 + i == K;
+    auto ld4 = [&](const __amdgpu_buffer_rsrc_t &r, int voff, int soff) {
+        return __builtin_bit_cast(v4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+    };
+    v4 acc[4][13];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int t = 0; t < 13; ++t) acc[u][t] = (v4){0.f, 0.f, 0.f, 0.f};
+    struct Frags { v4 pg[3][4]; v4 pl; v4 q[4]; };                 // [group][step], plain tile [step], [step]
+    auto load = [&](Frags &f, int64_t rb, bool tail) {
+        const int sp = (int)rb * DP * 4, sq = (int)rb * DQ * 4;
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const DwTail tl = tail ? dw_tail(rb, 4 * s4 + g, S.nr) : DwTail{true, 0};
+            const int back_p = tl.back * DP * 4, back_q = tl.back * DQ * 4;
+            f.q[s4] = ld4(S.rq, offq - back_q, sq + s4 * 16 * DQ);
+#pragma unroll
+            for (int G = 0; G < 3; ++G) f.pg[G][s4] = ld4(S.rp, offpg + 256 * G - back_p, sp + s4 * 16 * DP);
+            f.pl[s4] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(S.rp, offpl - back_p, sp + s4 * 16 * DP, 0));
+            if (!tl.ok) {
+                if (P_IS_N) {
+#pragma unroll
+                    for (int G = 0; G < 3; ++G) f.pg[G][s4] = (v4){0.f, 0.f, 0.f, 0.f};
+                    f.pl[s4] = 0.f;
+                } else {
+                    f.q[s4] = (v4){0.f, 0.f, 0.f, 0.f};
+                }
+            }
+        }
+    };
+    auto mma = [&](Frags &f) {
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            if (P_IS_N) f.q[s4][0] = q_one ? 1.0f : f.q[s4][0];
+            else f.pl[s4] = p_one ? 1.0f : f.pl[s4];
+        }
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                for (int G = 0; G < 3; ++G)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[u][4 * G + j] = MF<float>::mma(f.q[s4][u], f.pg[G][s4][j], acc[u][4 * G + j]);
+                acc[u][12] = MF<float>::mma(f.q[s4][u], f.pl[s4], acc[u][12]);
+            }
+    };
+    Frags fa, fb;
+    dw_rows_f32(S.nr, fa, fb, load, mma);
+    dw_store_strided<P_IS_N>(acc, slab + (int64_t)blockIdx.y * slab_size, gq, g, i, N, K);
+}
+
 // The same two products on v_mfma_f32_16x16x32_bf16, for BAMD_MODE_BF16 handles: operands rounded to bfloat16 from the float32 rows on
 // load, float32 accumulation, float32 partial gradients.  The contraction index of that MFMA holds EIGHT consecutive batch rows per
 // lane: lane (g, i) loads columns 4 i .. 4 i + 3 of rows 8 g + e (e = 0..7) of a 32-row block -- 16-byte loads, 4 rows x 256 contiguous
@@ -746,23 +795,12 @@ __global__ void __launch_bounds__(256) dw_wide_bf16_k(const float *__restrict__ 
                                                       int64_t rps, float *__restrict__ slab, int64_t slab_size) {
     static_assert(!(Q16 && P_IS_N), "the bfloat16 operand is dZ on the Q side");
     using v4 = MF<float>::v4;
-    typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
     constexpr int qes = Q16 ? 2 : 4;                               // bytes per stored element of Q
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
-    const float *__restrict__ pm = P_IS_N ? dzm : xm;
-    const float *__restrict__ qm = P_IS_N ? xm : dzm;
-    const int DP = P_IS_N ? N : K, DQ = P_IS_N ? K : N;
-    const int CQ = P_IS_N ? K + 1 : N;
     const int gq = (int)blockIdx.x * 4 + wave;
-    if (64 * gq >= CQ) return;
-    const int64_t r_begin = (int64_t)blockIdx.y * rps;
-    const int64_t r_end = r_begin + rps < rows ? r_begin + rps : rows;
-    if (r_begin >= r_end) return;
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void *)(pm + r_begin * DP), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)qm + r_begin * DQ * qes), 0, 0x7fffffff, 0x00020000);
+    DwSplit S;
+    if (!dw_split<P_IS_N>(S, dzm, xm, N, K, rows, rps, 64 * gq, qes)) return;
+    const int DP = S.DP, DQ = S.DQ;
     const int cq = 64 * gq + 4 * i;
     const int offq = (8 * g * DQ + (cq + 4 <= DQ ? cq : DQ - 4)) * qes;
     const int offpg = (8 * g * DP + 4 * i) * 4;
@@ -779,25 +817,18 @@ __global__ void __launch_bounds__(256) dw_wide_bf16_k(const float *__restrict__ 
         for (int t = 0; t < 13; ++t) acc[u][t] = (v4){0.f, 0.f, 0.f, 0.f};
     struct Raw { v4 pg[3][8]; float pl[8]; v4 q[8]; u2 q16[8]; };  // [group][row e], plain tile [row e], [row e] (q16: Q16)
     struct Pk { bf8 p[13]; bf8 q[4]; };
-    const int64_t nr = r_end - r_begin;
     auto load = [&](Raw &f, int64_t rb, bool tail) {
         const int sp = (int)rb * DP * 4, sq = (int)rb * DQ * qes;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            int back_p = 0, back_q = 0;
-            bool ok = true;
-            if (tail) {                                            // rows beyond the range read its last row, dZ zeroed
-                ok = rb + 8 * g + e < nr;
-                const int back = ok ? 0 : (int)(rb + 8 * g + e - (nr - 1));
-                back_p = back * DP * 4;
-                back_q = back * DQ * qes;
-            }
-            if constexpr (Q16) f.q16[e] = __builtin_bit_cast(u2, __builtin_amdgcn_raw_buffer_load_b64(rq, offq - back_q, sq + e * qes * DQ, 0));
-            else f.q[e] = ld4(rq, offq - back_q, sq + e * 4 * DQ);
+            const DwTail tl = tail ? dw_tail(rb, 8 * g + e, S.nr) : DwTail{true, 0};
+            const int back_p = tl.back * DP * 4, back_q = tl.back * DQ * qes;
+            if constexpr (Q16) f.q16[e] = __builtin_bit_cast(u2, __builtin_amdgcn_raw_buffer_load_b64(S.rq, offq - back_q, sq + e * qes * DQ, 0));
+            else f.q[e] = ld4(S.rq, offq - back_q, sq + e * 4 * DQ);
 #pragma unroll
-            for (int G = 0; G < 3; ++G) f.pg[G][e] = ld4(rp, offpg + 256 * G - back_p, sp + e * 4 * DP);
-            f.pl[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, offpl - back_p, sp + e * 4 * DP, 0));
-            if (tail && !ok) {
+            for (int G = 0; G < 3; ++G) f.pg[G][e] = ld4(S.rp, offpg + 256 * G - back_p, sp + e * 4 * DP);
+            f.pl[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(S.rp, offpl - back_p, sp + e * 4 * DP, 0));
+            if (!tl.ok) {
                 if (P_IS_N) {
 #pragma unroll
                     for (int G = 0; G < 3; ++G) f.pg[G][e] = (v4){0.f, 0.f, 0.f, 0.f};
@@ -809,12 +840,6 @@ __global__ void __launch_bounds__(256) dw_wide_bf16_k(const float *__restrict__ 
             }
         }
     };
-    auto pack8 = [&](float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7) {
-        const bf2 p0 = {(__bf16)a0, (__bf16)a1}, p1 = {(__bf16)a2, (__bf16)a3}, p2 = {(__bf16)a4, (__bf16)a5}, p3 = {(__bf16)a6, (__bf16)a7};
-        const u4 w = {__builtin_bit_cast(unsigned, p0), __builtin_bit_cast(unsigned, p1), __builtin_bit_cast(unsigned, p2),
-                      __builtin_bit_cast(unsigned, p3)};
-        return __builtin_bit_cast(bf8, w);
-    };
     auto pack = [&](Pk &k, Raw &f) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -824,10 +849,8 @@ __global__ void __launch_bounds__(256) dw_wide_bf16_k(const float *__restrict__ 
 #pragma unroll
         for (int G = 0; G < 3; ++G)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                k.p[4 * G + j] = pack8(f.pg[G][0][j], f.pg[G][1][j], f.pg[G][2][j], f.pg[G][3][j], f.pg[G][4][j], f.pg[G][5][j], f.pg[G][6][j],
-                                       f.pg[G][7][j]);
-        k.p[12] = pack8(f.pl[0], f.pl[1], f.pl[2], f.pl[3], f.pl[4], f.pl[5], f.pl[6], f.pl[7]);
+            for (int j = 0; j < 4; ++j) k.p[4 * G + j] = pack8([&](int e) { return f.pg[G][e][j]; });
+        k.p[12] = pack8([&](int e) { return f.pl[e]; });
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if constexpr (Q16) {      // column u of rows e = 2 d, 2 d + 1 -> dword d of the operand: halves picked by v_perm_b32
@@ -837,7 +860,7 @@ __global__ void __launch_bounds__(256) dw_wide_bf16_k(const float *__restrict__ 
                     w[d] = __builtin_amdgcn_perm(f.q16[2 * d + 1][u >> 1], f.q16[2 * d][u >> 1], (u & 1) ? 0x07060302u : 0x05040100u);
                 k.q[u] = __builtin_bit_cast(bf8, w);
             } else {
-                k.q[u] = pack8(f.q[0][u], f.q[1][u], f.q[2][u], f.q[3][u], f.q[4][u], f.q[5][u], f.q[6][u], f.q[7][u]);
+                k.q[u] = pack8([&](int e) { return f.q[e][u]; });
             }
         }
     };
@@ -849,60 +872,8 @@ __global__ void __launch_bounds__(256) dw_wide_bf16_k(const float *__restrict__ 
     };
     Raw ra;
     Pk pk;
-    const int64_t nfull = nr >> 5;
-    if (nfull > 0) {
-        load(ra, 0, false);
-        for (int64_t b = 0; b < nfull; ++b) {
-            pack(pk, ra);
-            __builtin_amdgcn_sched_barrier(0);
-            if (b + 1 < nfull) load(ra, 32 * (b + 1), false);      // the next block's rows stream in behind this block's MFMAs
-            __builtin_amdgcn_sched_barrier(0);
-            mma(pk);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    if (nr & 31) {
-        load(ra, 32 * nfull, true);
-        pack(pk, ra);
-        mma(pk);
-    }
-    // C map: as dw_wide_k (register r of lane (g, i) in accumulator (u, t): Q column 64 gq + 16 g + 4 r + u; P column 64 G + 4 i + j for
-    // the strided tile t = 4 G + j, 192 + i for the plain tile t = 12)
-    float *out = slab + (int64_t)blockIdx.y * slab_size;
-    if (P_IS_N) {
-#pragma unroll
-        for (int t = 0; t < 13; ++t) {
-            const int n = t < 12 ? 64 * (t >> 2) + 4 * i + (t & 3) : 192 + i;
-            if (n >= N) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k0 = 64 * gq + 16 * g + 4 * r;
-                if (k0 + 3 < K) {
-                    *(v4 *)(out + (int64_t)n * K + k0) = (v4){acc[0][t][r], acc[1][t][r], acc[2][t][r], acc[3][t][r]};
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (k0 + u < K) out[(int64_t)n * K + k0 + u] = acc[u][t][r];
-                        else if (k0 + u == K) out[(int64_t)N * K + n] = acc[u][t][r];
-                    }
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = 64 * gq + 16 * g + 4 * r + u;
-                if (n >= N) continue;
-#pragma unroll
-                for (int G = 0; G < 3; ++G)
-                    *(v4 *)(out + (int64_t)n * K + 64 * G + 4 * i) = (v4){acc[u][4 * G][r], acc[u][4 * G + 1][r], acc[u][4 * G + 2][r], acc[u][4 * G + 3][r]};
-                const int k = 192 + i;
-                if (k < K) out[(int64_t)n * K + k] = acc[u][12][r];
-                else if (k == K) out[(int64_t)N * K + n] = acc[u][12][r];
-            }
-    }
+    dw_rows_bf16(S.nr, ra, pk, load, pack, mma);
+    dw_store_strided<P_IS_N>(acc, slab + (int64_t)blockIdx.y * slab_size, gq, g, i, N, K);
 }
 
 // dw_short_k's plain tiles on the bf16 MFMA, for the wide weight gradients of a BAMD_MODE_BF16 handle whose rows are not 16-byte
@@ -913,28 +884,18 @@ template <int PT, int TQ, bool P_IS_N>
 __global__ void __launch_bounds__(256) dw_short_bf16_k(const float *__restrict__ dzm, const float *__restrict__ xm, int N, int K, int64_t rows,
                                                        int64_t rps, float *__restrict__ slab, int64_t slab_size) {
     using v4 = MF<float>::v4;
-    typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
-    const float *__restrict__ pm = P_IS_N ? dzm : xm;
-    const float *__restrict__ qm = P_IS_N ? xm : dzm;
-    const int DP = P_IS_N ? N : K, DQ = P_IS_N ? K : N;
-    const int CQ = P_IS_N ? K + 1 : N;
     const int qt0 = ((int)blockIdx.x * 4 + wave) * TQ;
-    if (qt0 * 16 >= CQ) return;
-    const int64_t r_begin = (int64_t)blockIdx.y * rps;
-    const int64_t r_end = r_begin + rps < rows ? r_begin + rps : rows;
-    if (r_begin >= r_end) return;
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void *)(pm + r_begin * DP), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)(qm + r_begin * DQ), 0, 0x7fffffff, 0x00020000);
+    DwSplit S;
+    if (!dw_split<P_IS_N>(S, dzm, xm, N, K, rows, rps, 16 * qt0)) return;
+    const int DP = S.DP, DQ = S.DQ;
     int offq[TQ];
     const int offp0 = (8 * g * DP + i) * 4;
     const int offpl = (8 * g * DP + (16 * (PT - 1) + i < DP ? 16 * (PT - 1) + i : DP - 1)) * 4;
 #pragma unroll
     for (int u = 0; u < TQ; ++u) { const int c = 16 * (qt0 + u) + i; offq[u] = (8 * g * DQ + (c < DQ ? c : DQ - 1)) * 4; }
-    auto ldp = [&](int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, voff, soff, 0)); };
-    auto ldq = [&](int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rq, voff, soff, 0)); };
+    auto ldp = [&](int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(S.rp, voff, soff, 0)); };
+    auto ldq = [&](int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(S.rq, voff, soff, 0)); };
     const bool p_one = !P_IS_N && 16 * (PT - 1) + i == K;
     bool q_one[TQ];
 #pragma unroll
@@ -946,34 +907,22 @@ __global__ void __launch_bounds__(256) dw_short_bf16_k(const float *__restrict__
         for (int t = 0; t < PT; ++t) acc[u][t] = (v4){0.f, 0.f, 0.f, 0.f};
     struct Raw { float p[PT][8]; float q[TQ][8]; };
     struct Pk { bf8 p[PT]; bf8 q[TQ]; };
-    const int64_t nr = r_end - r_begin;
     auto load = [&](Raw &f, int64_t rb, bool tail) {
         const int sp = (int)rb * DP * 4, sq = (int)rb * DQ * 4;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            bool ok = true;
-            int back = 0;
-            if (tail) {                                            // rows beyond the range read its last row, dZ zeroed
-                ok = rb + 8 * g + e < nr;
-                back = ok ? 0 : (int)(rb + 8 * g + e - (nr - 1));
-            }
+            const DwTail tl = tail ? dw_tail(rb, 8 * g + e, S.nr) : DwTail{true, 0};
 #pragma unroll
             for (int u = 0; u < TQ; ++u) {
-                const float v = ldq(offq[u] - back * DQ * 4, sq + e * 4 * DQ);
-                f.q[u][e] = (tail && !P_IS_N && !ok) ? 0.f : v;
+                const float v = ldq(offq[u] - tl.back * DQ * 4, sq + e * 4 * DQ);
+                f.q[u][e] = (!P_IS_N && !tl.ok) ? 0.f : v;
             }
 #pragma unroll
             for (int t = 0; t < PT; ++t) {
-                const float v = ldp((t == PT - 1 ? offpl : offp0 + 64 * t) - back * DP * 4, sp + e * 4 * DP);
-                f.p[t][e] = (tail && P_IS_N && !ok) ? 0.f : v;
+                const float v = ldp((t == PT - 1 ? offpl : offp0 + 64 * t) - tl.back * DP * 4, sp + e * 4 * DP);
+                f.p[t][e] = (P_IS_N && !tl.ok) ? 0.f : v;
             }
         }
-    };
-    auto pack8 = [&](const float (&a)[8]) {
-        const bf2 p0 = {(__bf16)a[0], (__bf16)a[1]}, p1 = {(__bf16)a[2], (__bf16)a[3]}, p2 = {(__bf16)a[4], (__bf16)a[5]}, p3 = {(__bf16)a[6], (__bf16)a[7]};
-        const u4 w = {__builtin_bit_cast(unsigned, p0), __builtin_bit_cast(unsigned, p1), __builtin_bit_cast(unsigned, p2),
-                      __builtin_bit_cast(unsigned, p3)};
-        return __builtin_bit_cast(bf8, w);
     };
     auto pack = [&](Pk &k, Raw &f) {
 #pragma unroll
@@ -985,9 +934,9 @@ __global__ void __launch_bounds__(256) dw_short_bf16_k(const float *__restrict__
             }
         }
 #pragma unroll
-        for (int t = 0; t < PT; ++t) k.p[t] = pack8(f.p[t]);
+        for (int t = 0; t < PT; ++t) k.p[t] = pack8([&](int e) { return f.p[t][e]; });
 #pragma unroll
-        for (int u = 0; u < TQ; ++u) k.q[u] = pack8(f.q[u]);
+        for (int u = 0; u < TQ; ++u) k.q[u] = pack8([&](int e) { return f.q[u][e]; });
     };
     auto mma = [&](const Pk &k) {
 #pragma unroll
@@ -997,50 +946,8 @@ __global__ void __launch_bounds__(256) dw_short_bf16_k(const float *__restrict__
     };
     Raw ra;
     Pk pk;
-    const int64_t nfull = nr >> 5;
-    if (nfull > 0) {
-        load(ra, 0, false);
-        for (int64_t b = 0; b < nfull; ++b) {
-            pack(pk, ra);
-            __builtin_amdgcn_sched_barrier(0);
-            if (b + 1 < nfull) load(ra, 32 * (b + 1), false);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(pk);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    if (nr & 31) {
-        load(ra, 32 * nfull, true);
-        pack(pk, ra);
-        mma(pk);
-    }
-    // C map: register r of lane (g, i) = (q column 4 g + r of the tile, p column i), as dw_short_k
-    float *out = slab + (int64_t)blockIdx.y * slab_size;
-#pragma unroll
-    for (int u = 0; u < TQ; ++u) {
-        const int q0 = 16 * (qt0 + u) + 4 * g;
-#pragma unroll
-        for (int t = 0; t < PT; ++t) {
-            const int pc = 16 * t + i;
-            if (P_IS_N) {
-                if (pc < N) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (q0 + r < K) out[(int64_t)pc * K + q0 + r] = acc[u][t][r];
-                        else if (q0 + r == K) out[(int64_t)N * K + pc] = acc[u][t][r];
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (q0 + r < N) {
-                        if (pc < K) out[(int64_t)(q0 + r) * K + pc] = acc[u][t][r];
-                        else if (pc == K) out[(int64_t)N * K + q0 + r] = acc[u][t][r];
-                    }
-                }
-            }
-        }
-    }
+    dw_rows_bf16(S.nr, ra, pk, load, pack, mma);
+    dw_store_plain<PT, TQ, P_IS_N>(acc, slab + (int64_t)blockIdx.y * slab_size, qt0, g, i, N, K);
 }
 
 // grads[off + j] (+)= sum over the layer's splits of slab_l[split][j], splits in fixed order
@@ -1268,42 +1175,35 @@ static ShortPlan plan_short_dw(const bamd_handle *h, int64_t rows) {
     pl.ok = true;
     return pl;
 }
-template <int PT>
-static void launch_dw_short(bool p_is_n, const float *dz, const float *xm, int N, int K, int64_t rows, int64_t rps, float *slab, dim3 grid,
-                            hipStream_t s) {
-    const int64_t size = (int64_t)N * K + N;
-    if (p_is_n) hipLaunchKernelGGL((dw_short_k<PT, 2, true>), grid, dim3(256), 0, s, dz, xm, N, K, rows, rps, slab, size);
-    else hipLaunchKernelGGL((dw_short_k<PT, 2, false>), grid, dim3(256), 0, s, dz, xm, N, K, rows, rps, slab, size);
-}
+// One layer's split-K launch.  bf16: the chunk's wide weight gradients take bf16 operands (ChunkRoute::bf16_ops); dz16: this layer's dZ
+// is stored as bfloat16 (the last layer of such a chunk, dz16_of).  The three run-time bools pick the instantiation; the arguments are
+// the same for all 17.
 static void run_dw_short(const ShortPlan &pl, int l, const float *dz, const float *xm, int N, int K, int64_t rows, float *slabs, bool bf16,
                          bool dz16, hipStream_t s) {
-    const dim3 grid((unsigned)pl.ncol[l], (unsigned)pl.nsplit[l]);
-    float *slab = slabs + pl.rp.base[l];
-    if (pl.wide[l]) {
-        const int64_t size = (int64_t)N * K + N;
-        if (bf16) {      // BAMD_MODE_BF16 handles: the two wide weight gradients on the bf16 MFMA (BALER_AMD_BF16_WIDE_TRAIN=0: float32)
-            if (pl.p_is_n[l]) hipLaunchKernelGGL((dw_wide_bf16_k<true>), grid, dim3(256), 0, s, dz, xm, N, K, rows, pl.rps[l], slab, size);
-            else if (dz16) hipLaunchKernelGGL((dw_wide_bf16_k<false, true>), grid, dim3(256), 0, s, dz, xm, N, K, rows, pl.rps[l], slab, size);
-            else hipLaunchKernelGGL((dw_wide_bf16_k<false>), grid, dim3(256), 0, s, dz, xm, N, K, rows, pl.rps[l], slab, size);
-            return;
-        }
-        if (pl.p_is_n[l]) hipLaunchKernelGGL((dw_wide_k<true>), grid, dim3(256), 0, s, dz, xm, N, K, rows, pl.rps[l], slab, size);
-        else hipLaunchKernelGGL((dw_wide_k<false>), grid, dim3(256), 0, s, dz, xm, N, K, rows, pl.rps[l], slab, size);
-        return;
-    }
-    if (bf16 && pl.pt[l] == 13) {      // a wide layer whose rows are not 16-byte aligned (625 columns), BAMD_MODE_BF16 handle
-        const int64_t size = (int64_t)N * K + N;
-        if (pl.p_is_n[l]) hipLaunchKernelGGL((dw_short_bf16_k<13, 2, true>), grid, dim3(256), 0, s, dz, xm, N, K, rows, pl.rps[l], slab, size);
-        else hipLaunchKernelGGL((dw_short_bf16_k<13, 2, false>), grid, dim3(256), 0, s, dz, xm, N, K, rows, pl.rps[l], slab, size);
-        return;
-    }
-    switch (pl.pt[l]) {
-    case 1: launch_dw_short<1>(pl.p_is_n[l], dz, xm, N, K, rows, pl.rps[l], slab, grid, s); break;
-    case 2: launch_dw_short<2>(pl.p_is_n[l], dz, xm, N, K, rows, pl.rps[l], slab, grid, s); break;
-    case 4: launch_dw_short<4>(pl.p_is_n[l], dz, xm, N, K, rows, pl.rps[l], slab, grid, s); break;
-    case 7: launch_dw_short<7>(pl.p_is_n[l], dz, xm, N, K, rows, pl.rps[l], slab, grid, s); break;
-    default: launch_dw_short<13>(pl.p_is_n[l], dz, xm, N, K, rows, pl.rps[l], slab, grid, s); break;
-    }
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.ncol[l], (unsigned)pl.nsplit[l]), dim3(256), 0, s, dz, xm, N, K, rows, pl.rps[l],
+                           slabs + pl.rp.base[l], (int64_t)N * K + N);
+    };
+    with_bool(pl.p_is_n[l], [&](auto p_is_n) {
+        with_bool(bf16, [&](auto b16) {
+            constexpr bool PN = decltype(p_is_n)::value, B16 = decltype(b16)::value;
+            if (pl.wide[l]) {      // 16-byte rows: strided tiles; on a BF16 handle the bf16 MFMA, dZ in 16 bits only as the Q side
+                if constexpr (!B16) launch(dw_wide_k<PN>);
+                else if constexpr (PN) launch(dw_wide_bf16_k<true>);
+                else with_bool(dz16, [&](auto q16) { launch(dw_wide_bf16_k<false, decltype(q16)::value>); });
+            } else if (B16 && pl.pt[l] == 13) {      // a wide layer whose rows are not 16-byte aligned (625 columns), BF16 handle
+                launch(dw_short_bf16_k<13, 2, PN>);
+            } else {
+                switch (pl.pt[l]) {
+                case 1: launch(dw_short_k<1, 2, PN>); break;
+                case 2: launch(dw_short_k<2, 2, PN>); break;
+                case 4: launch(dw_short_k<4, 2, PN>); break;
+                case 7: launch(dw_short_k<7, 2, PN>); break;
+                default: launch(dw_short_k<13, 2, PN>); break;
+                }
+            }
+        });
+    });
 }
 
 // ---- all weight gradients of a SMALL float32 batch in one launch ----------------------------------------------------------------------
@@ -1417,8 +1317,11 @@ __global__ void __launch_bounds__(256) dw_small_all_k(SmallDwPlan<T> pl, int64_t
 struct ChunkRoute {
     bool wide;        // row-local work on the two fused wide launches of fused.hip
     bool small_wide;  // ... on their split float32 forms (also on a BF16 handle)
-    bool bf16_dw;     // BF16 handle whose weight gradients keep the per-layer launches (bf16 operands where the layer is wide)
+    bool bf16_dw;     // BF16 handle whose weight gradients keep the per-layer launches: never dw_small_all_k
+    bool bf16_ops;    // ... and those launches take bf16 operands where the layer is wide: wide && bf16_dw
     bool dw_small;    // every weight gradient (+ the loss sum, + Adam when asked) in ONE launch: dw_small_all_k
+    // bf16_dw does not ask for `wide`: a BF16 handle of the 24-column model that comes here through bamd_fwd_bwd_latent stays off
+    // dw_small_all_k and runs the float32 per-layer kernels (bf16_ops is false).  That is how it has always run; the tests hold it so.
 };
 template <typename T>
 static ChunkRoute route_chunk(const bamd_handle *h, int64_t rows) {
@@ -1428,9 +1331,16 @@ static ChunkRoute route_chunk(const bamd_handle *h, int64_t rows) {
     const int64_t lw_rows = env_ll("BALER_AMD_WIDE_LAYERWISE_ROWS", 0);
     r.wide = sizeof(T) == 4 && fused_wide_train(h) && !(rows <= lw_rows && rows <= gemm_small_rows() && h->mode != BAMD_MODE_BF16);
     r.small_wide = r.wide && fused_wide_small(h, rows);      // (a BF16 handle's small batches run the float32 split launches)
-    r.bf16_dw = h->mode == BAMD_MODE_BF16 && !env_off("BALER_AMD_BF16_WIDE_TRAIN") && !r.small_wide;
+    r.bf16_dw = h->mode == BAMD_MODE_BF16 && !env_off("BALER_AMD_BF16_WIDE_TRAIN") && !r.small_wide;      // (=0: float32 operands)
+    r.bf16_ops = r.wide && r.bf16_dw;
     r.dw_small = !r.bf16_dw && rows <= dw_small_rows() && h->L <= 8;
     return r;
+}
+// dL/drecon stored as bfloat16: when both of its readers take it that way -- the fused backward launch and the last layer's weight
+// gradient as dw_wide_bf16_k's Q side.  fused_wide_train_forward writes what this says and run_dw_short reads what this says.
+static bool dz16_of(const ChunkRoute &r, const ShortPlan &sp, const bamd_handle *h) {
+    const int ll = h->L - 1;
+    return r.bf16_ops && sp.ok && sp.wide[ll] && !sp.p_is_n[ll] && h->dims[ll + 1] % 4 == 0 && !env_off("BALER_AMD_BF16_DZ16");      // (=0: float32)
 }
 
 template <typename T>
@@ -1473,16 +1383,9 @@ static int fwd_bwd_T(bamd_handle *h, const void *x, int x_dtype, int64_t n, cons
         }
         // wide models in float32: the row-local work (forward, loss, input-gradient chain) as two fused launches (fused.hip)
         const ChunkRoute route = route_chunk<T>(h, rows);
-        const bool wide = route.wide, small_wide = route.small_wide;
-        // BF16 handles: dL/drecon stored as bfloat16 when its two readers take it that way (BALER_AMD_BF16_DZ16=0: float32)
-        bool dz16 = false;
-        if constexpr (sizeof(T) == 4) {
-            const char *e = getenv("BALER_AMD_BF16_WIDE_TRAIN"), *e16 = getenv("BALER_AMD_BF16_DZ16");
-            const int ll = h->L - 1;
-            dz16 = wide && !small_wide && h->mode == BAMD_MODE_BF16 && !(e && e[0] == '0') && !(e16 && e16[0] == '0') && sp.ok && sp.wide[ll] &&
-                   !sp.p_is_n[ll] && h->dims[ll + 1] % 4 == 0;
-            if (wide) fused_wide_set_dz16(h, dz16);
-        }
+        const bool wide = route.wide;
+        const bool dz16 = dz16_of(route, sp, h);
+        if (wide) fused_wide_set_dz16(h, dz16);
         int nblk = 0;
         if (wide) {
             rc = h->lossp.ensure(sizeof(double) * 4096);
@@ -1520,25 +1423,21 @@ static int fwd_bwd_T(bamd_handle *h, const void *x, int x_dtype, int64_t n, cons
                                            latent_grad ? (const float *)latent_grad + r0 * h->dims[h->L / 2] : nullptr, s);
             if (rc) return rc;
         }
-        // small float32 batches of a model on the fused row-local launches: every weight gradient in ONE launch, straight into `grads`
         for (int l = h->L - 1; l >= 0; --l) {
             int K = h->dims[l], N = h->dims[l + 1];
             const T *dz = wk.dz[l];
-            // [dW | db] = dZ^T [X | 1], reduced over this chunk's rows in nsplit fixed slabs
-            if (dw_small) {
-            } else if (sp.ok) {
-                if constexpr (sizeof(T) == 4) {
-                    const char *e = getenv("BALER_AMD_BF16_WIDE_TRAIN");
-                    const bool bf16 = wide && !small_wide && h->mode == BAMD_MODE_BF16 && !(e && e[0] == '0');
-                    run_dw_short(sp, l, dz, l == 0 ? x0 : wk.y[l], N, K, rows, slabs, bf16, dz16 && l == h->L - 1, s);
+            // [dW | db] = dZ^T [X | 1], reduced over this chunk's rows in nsplit fixed slabs (dw_small: one launch behind this loop)
+            if (!dw_small) {
+                if (sp.ok) {
+                    if constexpr (sizeof(T) == 4) run_dw_short(sp, l, dz, l == 0 ? x0 : wk.y[l], N, K, rows, slabs, route.bf16_ops, dz16 && l == h->L - 1, s);
+                } else {
+                    Opnd<T> A{dz, 1, N, N, -1};
+                    Opnd<T> B{l == 0 ? x0 : wk.y[l], 1, K, K, K};
+                    Epi<T> e{};
+                    e.n_rows = N; e.kin = K; e.gw = slabs + h->w_off[l]; e.gb = slabs + h->b_off[l];
+                    e.slab_stride = np; e.rows_per_split = rps;
+                    launch_gemm<T, EPI_DW, false, false>(A, B, rows, e, N, K + 1, (unsigned)nsplit, s);
                 }
-            } else {
-                Opnd<T> A{dz, 1, N, N, -1};
-                Opnd<T> B{l == 0 ? x0 : wk.y[l], 1, K, K, K};
-                Epi<T> e{};
-                e.n_rows = N; e.kin = K; e.gw = slabs + h->w_off[l]; e.gb = slabs + h->b_off[l];
-                e.slab_stride = np; e.rows_per_split = rps;
-                launch_gemm<T, EPI_DW, false, false>(A, B, rows, e, N, K + 1, (unsigned)nsplit, s);
             }
             if (l > 0 && !wide) {
                 // dZ_{l-1} = (dZ_l W_l) * lrelu'(Y_{l-1})
@@ -1569,8 +1468,6 @@ static int fwd_bwd_T(bamd_handle *h, const void *x, int x_dtype, int64_t n, cons
             if constexpr (sizeof(T) == 4) { if (adam) sa = *adam; }
             hipLaunchKernelGGL(dw_small_all_k<T>, dim3((unsigned)((t0 + 3) / 4 + 1)), dim3(256), 0, s, pl, rows, grads, chunk_i > 0 ? 1 : 0, sa,
                                (const double *)h->lossp.p, nblk, 1.0 / c, (int64_t)np);
-        }
-        if (dw_small) {
         } else if (sp.ok) {
             if constexpr (sizeof(T) == 4)
                 hipLaunchKernelGGL(reduce_layers_k, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, (const float *)slabs, sp.rp, grads,

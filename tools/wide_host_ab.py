@@ -35,12 +35,51 @@ def bits(t):
     return t.contiguous().view(torch.int64 if t.dtype == torch.float64 else torch.int32)
 
 
-def main():
-    args = [a for a in sys.argv[1:] if a != "--branch-first"]      # --branch-first: the branch's library and handles are created first
+def ab_line(label, who, call, outs):
+    """One line: call(w) for w in `who` = ["parent", "branch"] (in creation order); outs(w) -> the tensors compared as bit patterns.
+    Prints the medians over ROUNDS rounds and whether branch - parent is within the parent's spread; returns (that, same bits)."""
+    for w in who:
+        call(w)
+    torch.cuda.synchronize()
+    same = all(torch.equal(bits(a), bits(b)) for a, b in zip(outs("parent"), outs("branch")))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    call("parent")
+    e1.record()
+    e1.synchronize()
+    ncall = int(min(50, max(3, 2.0 / max(e0.elapsed_time(e1), 1e-3))))      # ~2 ms per sample
+    for w in who:
+        for _ in range(ncall):
+            call(w)
+    us = {w: [] for w in who}
+    for r in range(ROUNDS):
+        for w in (("parent", "branch") if r % 2 == 0 else ("branch", "parent")):
+            e0.record()
+            for _ in range(ncall):
+                call(w)
+            e1.record()
+            e1.synchronize()
+            us[w].append(1e3 * e0.elapsed_time(e1) / ncall)
+    pm, bm = float(np.median(us["parent"])), float(np.median(us["branch"]))
+    spread = max(us["parent"]) - min(us["parent"])
+    inside = bm - pm <= spread
+    print(f"{label} parent med {pm:9.2f} us  min {min(us['parent']):9.2f}  max {max(us['parent']):9.2f}  "
+          f"(spread {spread:7.2f}) | branch med {bm:9.2f}  min {min(us['branch']):9.2f}  max {max(us['branch']):9.2f} | "
+          f"branch - parent {bm - pm:+8.2f} us: {'WITHIN' if inside else 'OUTSIDE'} spread; same bits: {same}", flush=True)
+    return inside, same
+
+
+def load_libs(argv):
+    """argv: PARENT_LIB [BRANCH_LIB] [--branch-first] -> {"parent": native module, "branch": native module}"""
+    args = [a for a in argv if a != "--branch-first"]      # --branch-first: the branch's library and handles are created first
     parent_lib = args[0]
     branch_lib = args[1] if len(args) > 1 else os.path.join(ROOT, "baler_amd", "libbaler_amd.so")
-    order = [("parent", parent_lib), ("branch", branch_lib)][::-1 if "--branch-first" in sys.argv else 1]
-    libs = {who: load_native("native_" + who, path) for who, path in order}
+    order = [("parent", parent_lib), ("branch", branch_lib)][::-1 if "--branch-first" in argv else 1]
+    return {who: load_native("native_" + who, path) for who, path in order}
+
+
+def main():
+    libs = load_libs(sys.argv[1:])
     outside = 0
     for (F, Z), mode, sizes in CASES:
         dims = [F, 200, 100, 50, Z, 50, 100, 200, F]
@@ -68,35 +107,7 @@ def main():
                 "fwd_bwd": (lambda w: hs[w].fwd_bwd(x, grads[w]), lambda w: [grads[w]]),
             }
             for what, (call, outs) in calls.items():
-                for w in hs:
-                    call(w)
-                torch.cuda.synchronize()
-                same = all(torch.equal(bits(a), bits(b)) for a, b in zip(outs("parent"), outs("branch")))
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                call("parent")
-                e1.record()
-                e1.synchronize()
-                ncall = int(min(50, max(3, 2.0 / max(e0.elapsed_time(e1), 1e-3))))      # ~2 ms per sample
-                for w in hs:
-                    for _ in range(ncall):
-                        call(w)
-                us = {w: [] for w in hs}
-                for r in range(ROUNDS):
-                    for w in (("parent", "branch") if r % 2 == 0 else ("branch", "parent")):
-                        e0.record()
-                        for _ in range(ncall):
-                            call(w)
-                        e1.record()
-                        e1.synchronize()
-                        us[w].append(1e3 * e0.elapsed_time(e1) / ncall)
-                pm, bm = float(np.median(us["parent"])), float(np.median(us["branch"]))
-                spread = max(us["parent"]) - min(us["parent"])
-                inside = bm - pm <= spread
-                outside += not inside
-                print(f"({F}, {Z}) {mode:5s} n={n:<6d} {what:13s} parent med {pm:9.2f} us  min {min(us['parent']):9.2f}  max {max(us['parent']):9.2f}  "
-                      f"(spread {spread:7.2f}) | branch med {bm:9.2f}  min {min(us['branch']):9.2f}  max {max(us['branch']):9.2f} | "
-                      f"branch - parent {bm - pm:+8.2f} us: {'WITHIN' if inside else 'OUTSIDE'} spread; same bits: {same}", flush=True)
+                outside += not ab_line(f"({F}, {Z}) {mode:5s} n={n:<6d} {what:13s}", list(hs), call, outs)[0]
     print(f"{outside} lines outside the parent's spread")
 
 
