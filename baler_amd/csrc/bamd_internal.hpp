@@ -122,6 +122,8 @@ int launch_convert(const void *src, int src_dtype, void *dst, int dst_dtype, int
                    hipStream_t s);
 int launch_emd_rows(const void *x, const void *recon, int dtype, int64_t n, int c, double *out,
                     hipStream_t s);
+int launch_emd_rows_wide(const void *x, const void *recon, int dtype, int64_t n, int c, double *out,
+                         hipStream_t s);   // emd.hip: 65 <= c <= 4096
 int launch_swd(const void *z, const void *prior, const void *proj, int dtype, int64_t n, int d, int ns, double reg_weight,
                double *loss_out, void *dz_out, hipStream_t s);
 int launch_error_deltas(const void *x, const void *recon, int dtype, int64_t n, double bound, uint8_t *flags, void *deltas,

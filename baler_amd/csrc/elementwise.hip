@@ -258,7 +258,8 @@ __global__ void sum_partials_k(const double *__restrict__ part, int n, double *_
 
 int launch_emd_rows(const void *x, const void *r, int dtype, int64_t n, int c, double *out,
                     hipStream_t s) {
-    BAMD_REQUIRE(x && r && out && n > 0 && c > 0 && c <= 64, "bad arguments (n_cols must be <= 64)");
+    BAMD_REQUIRE(x && r && out && n > 0 && c > 0 && c <= 4096, "bad arguments (n_cols must be <= 4096)");
+    if (c > 64) return launch_emd_rows_wide(x, r, dtype, n, c, out, s);      // emd.hip: rows sorted in LDS
     int nblk = (int)((n + 255) / 256 < 512 ? (n + 255) / 256 : 512);
     DevBuf &scratch = scratch_for(1, s);
     int rc = scratch.ensure(sizeof(double) * nblk);

@@ -13,13 +13,10 @@
 // Batches above 4096 rows (CFD_project_animation_config.py:19: batch_size = 6000) run the same bitonic network in passes
 // through global memory (swd_project_k / swd_local_k / swd_global_k / swd_finish_k below).
 #include "bamd_internal.hpp"
+#include "bitonic.hpp"
 
 namespace bamd {
 namespace {
-
-template <typename T> __device__ __forceinline__ T pos_inf();
-template <> __device__ __forceinline__ float pos_inf<float>() { return __int_as_float(0x7f800000); }
-template <> __device__ __forceinline__ double pos_inf<double>() { return __longlong_as_double(0x7ff0000000000000LL); }
 
 template <typename T>
 __global__ void __launch_bounds__(256) swd_sort_k(const T *__restrict__ z, const T *__restrict__ prior,
@@ -44,24 +41,9 @@ __global__ void __launch_bounds__(256) swd_sort_k(const T *__restrict__ z, const
         av[i] = a; bv[i] = b; ai[i] = i;
     }
     __syncthreads();
-    for (int k = 2; k <= m; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < m / 2; t += 256) {
-                const int lo = ((t / j) * 2 * j) + (t % j), hi = lo + j;
-                const bool up = (lo & k) == 0;
-                {
-                    const T x = av[lo], y = av[hi];
-                    const int xi = ai[lo], yi = ai[hi];
-                    const bool gt = x > y || (x == y && xi > yi);
-                    if (gt == up) { av[lo] = y; av[hi] = x; ai[lo] = yi; ai[hi] = xi; }
-                }
-                {
-                    const T x = bv[lo], y = bv[hi];
-                    if ((x > y) == up) { bv[lo] = y; bv[hi] = x; }
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_network(m, 0, 2, m, tid, 256,
+                    [&](int lo, int hi, bool up) { bitonic_cmpx(av[lo], av[hi], ai[lo], ai[hi], up); bitonic_cmpx(bv[lo], bv[hi], up); },
+                    [] { __syncthreads(); });
     double acc = 0.0;
     for (int i = tid; i < n; i += 256) {
         const T w = av[i] - bv[i];
@@ -94,10 +76,6 @@ __global__ void __launch_bounds__(256) swd_project_k(const T *__restrict__ z, co
     }
     AV[(int64_t)s * m + i] = a; BV[(int64_t)s * m + i] = b; AI[(int64_t)s * m + i] = i;
 }
-template <typename T> __device__ __forceinline__ void swd_cmpx(T &x, T &y, int &xi, int &yi, bool up) {
-    const bool gt = x > y || (x == y && xi > yi);
-    if (gt == up) { const T t = x; x = y; y = t; const int ti = xi; xi = yi; yi = ti; }
-}
 // all steps (k, j) with k in [k_lo, k_hi], j < min(k, chunk): inside LDS, one chunk per workgroup (direction from the GLOBAL index)
 template <typename T>
 __global__ void __launch_bounds__(256) swd_local_k(T *__restrict__ AV, T *__restrict__ BV, int *__restrict__ AI, int m, int k_lo, int k_hi) {
@@ -109,17 +87,9 @@ __global__ void __launch_bounds__(256) swd_local_k(T *__restrict__ AV, T *__rest
     const int g0 = blockIdx.x * kSwdChunk;
     for (int i = threadIdx.x; i < kSwdChunk; i += 256) { av[i] = AV[base + i]; bv[i] = BV[base + i]; ai[i] = AI[base + i]; }
     __syncthreads();
-    for (int k = k_lo; k <= k_hi; k <<= 1)
-        for (int j = (k >> 1) < kSwdChunk ? (k >> 1) : (kSwdChunk >> 1); j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < kSwdChunk / 2; t += 256) {
-                const int lo = ((t / j) * 2 * j) + (t % j), hi = lo + j;
-                const bool up = ((g0 + lo) & k) == 0;
-                swd_cmpx(av[lo], av[hi], ai[lo], ai[hi], up);
-                const T x = bv[lo], y = bv[hi];
-                if ((x > y) == up) { bv[lo] = y; bv[hi] = x; }
-            }
-            __syncthreads();
-        }
+    bitonic_network(kSwdChunk, g0, k_lo, k_hi, threadIdx.x, 256,
+                    [&](int lo, int hi, bool up) { bitonic_cmpx(av[lo], av[hi], ai[lo], ai[hi], up); bitonic_cmpx(bv[lo], bv[hi], up); },
+                    [] { __syncthreads(); });
     for (int i = threadIdx.x; i < kSwdChunk; i += 256) { AV[base + i] = av[i]; BV[base + i] = bv[i]; AI[base + i] = ai[i]; }
 }
 template <typename T>
@@ -127,14 +97,10 @@ __global__ void __launch_bounds__(256) swd_global_k(T *__restrict__ AV, T *__res
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= m / 2) return;
     const int64_t base = (int64_t)blockIdx.y * m;
-    const int lo = ((t / j) * 2 * j) + (t % j), hi = lo + j;
-    const bool up = (lo & k) == 0;
-    T x = AV[base + lo], y = AV[base + hi];
-    int xi = AI[base + lo], yi = AI[base + hi];
-    const bool gt = x > y || (x == y && xi > yi);
-    if (gt == up) { AV[base + lo] = y; AV[base + hi] = x; AI[base + lo] = yi; AI[base + hi] = xi; }
-    x = BV[base + lo]; y = BV[base + hi];
-    if ((x > y) == up) { BV[base + lo] = y; BV[base + hi] = x; }
+    const int lo = bitonic_lo(t, j), hi = lo + j;
+    const bool up = bitonic_up(lo, k);
+    bitonic_cmpx(AV[base + lo], AV[base + hi], AI[base + lo], AI[base + hi], up);
+    bitonic_cmpx(BV[base + lo], BV[base + hi], up);
 }
 // per projection: loss partial + gradient w.r.t. the projected values, scattered back to row order
 template <typename T>

@@ -218,6 +218,9 @@ def renormalize(x, features, int_mask=None):
 
 
 def emd_rows(x, recon):
+    """Sum over rows of the 1-D Wasserstein distance between the row's columns of x and recon (bamd_emd_rows): x, recon (n, c)
+    f32/f64 with c <= 4096 -> float64[1]; a wider table raises NativeError.  Exact sort, differences in float64, fixed-order sums
+    (bitwise repeatable, whatever BALER_AMD_EMD_WGS says).  A NaN in either table gives NaN; +-inf sort as values."""
     x = _dev_tensor(x)
     recon = _dev_tensor(recon)
     if x.dtype != recon.dtype or x.shape != recon.shape:

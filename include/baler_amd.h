@@ -409,7 +409,13 @@ int bamd_train_epoch_dp(bamd_handle *h, const void *x, int x_dtype, const int64_
 /* ---- diagnostics -------------------------------------------------------------------------------
  * Replaces: the EMD term of utils.mse_loss_emd_l1 (utils.py:112-119): sum over rows of the 1-D
  * Wasserstein distance between the row's column values of x and recon.  *out (device, float64)
- * is overwritten.  Forward-only metric; n_cols <= 64. */
+ * is overwritten.  Forward-only metric; n_cols <= 4096 (more is refused with BAMD_ERR_INVALID).
+ * Per row: mean_k |sort(x_row)_k - sort(recon_row)_k|; keys are compared in `dtype` and only ever moved, so the
+ * sort is exact, and the differences are formed in float64.  A NaN anywhere in x or recon makes *out NaN.
+ * +-inf sort as values: +inf at the same rank on both sides gives NaN (inf - inf), on one side only +inf.
+ * Every sum has a fixed order that depends on the table's shape alone: the result is bitwise repeatable and
+ * does not depend on how many workgroups ran (BALER_AMD_EMD_WGS, read per call, lowers the grid of the
+ * 65 .. 4096-column kernel).  Up to 64 columns: one thread per row; above: rows sorted in LDS (emd.hip). */
 int bamd_emd_rows(const void *x, const void *recon, int dtype, int64_t n_rows, int n_cols,
                   double *out, void *stream);
 /* ---- error-bounded deltas side channel (config.save_error_bounded_deltas) -------------------------
