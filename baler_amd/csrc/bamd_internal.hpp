@@ -192,6 +192,20 @@ inline AdamScalars adam_scalars(const bamd_adam &hp) {
     const double bc2 = 1.0 - pow(hp.beta2, (double)hp.step);
     return {hp.beta1, hp.beta2, hp.eps, hp.lr / bc1, sqrt(bc2)};
 }
+// Where the state of one Adam step lives, and its scalars: what a weight-gradient kernel that applies Adam to the parameters it owns
+// takes.  pcopy: the handle's own copy of the parameters; packed / sc_off / sc_idx: the fragment-packed copy and the CSR lists
+// parameter -> packed positions it is refreshed through (null: none).
+template <typename T> struct AdamTargets {
+    T *params, *pcopy, *m, *v, *packed;
+    const int *sc_off, *sc_idx;
+    double *loss_accum;
+    AdamScalars s;
+};
+template <typename T>
+inline AdamTargets<T> adam_targets(const bamd_handle *h, void *params, void *m, void *v, void *packed, const void *sc_off, const void *sc_idx,
+                                   double *loss_accum, const bamd_adam &hp) {
+    return {(T *)params, (T *)h->params.p, (T *)m, (T *)v, (T *)packed, (const int *)sc_off, (const int *)sc_idx, loss_accum, adam_scalars(hp)};
+}
 
 #if defined(__HIPCC__)
 // torch.optim.Adam single-tensor step (training.py:266; torch/optim/adam.py _single_tensor_adam) of one element.  The arithmetic

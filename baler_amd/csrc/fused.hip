@@ -20,6 +20,7 @@
 // fragment order (plain 16-byte stores, no atomics) and a small kernel sums the slabs in a fixed order
 // into the canonical state-dict layout: bitwise reproducible.
 #include "fused.hpp"
+#include "small_step.hpp"
 
 #include <climits>
 #include <cmath>
@@ -32,11 +33,6 @@ namespace {
 
 using v4 = float __attribute__((ext_vector_type(4)));
 
-__host__ __device__ constexpr int tiles(int d) { return (d + 15) / 16; }
-// MFMA steps needed for feature tile t of a dimension d (4 for full tiles, ceil(valid/4) for the last)
-__host__ __device__ constexpr int tile_steps(int d, int t) {
-    return d - 16 * t >= 16 ? 4 : (d - 16 * t + 3) / 4;
-}
 // feature held by slot (tile t, lane group g, register r); -1 = padding.  Full tiles: 16t + 4g + r
 // (4 consecutive features per lane: vector I/O); partial last tile: 16t + 4r + g (fills registers first).
 __host__ __device__ constexpr int slot_feature(int d, int t, int g, int r) {
@@ -53,22 +49,17 @@ constexpr int kRowsPerWG = 64;
 // kernel.  A cut at the bottleneck (16-float hand-off, encoder forward recomputed) measured 3.91 ms against 3.59 ms
 // per 1M rows (profiles/README.md), so the cut is written into the layouts below as what it is.
 
-// ---- compile-time description of AE(F, Z): 8 layers F-200-100-50-Z-50-100-200-F -----------------------
-template <int F, int Z> struct Net {
-    static constexpr int L = 8;
-    __host__ __device__ static constexpr int dim(int i) {
-        return i == 0 ? F : i == 1 ? 200 : i == 2 ? 100 : i == 3 ? 50 : i == 4 ? Z : i == 5 ? 50 : i == 6 ? 100 : i == 7 ? 200 : F;
-    }
-    __host__ __device__ static constexpr bool act(int l) { return !(l == 3 || l == 7); }
+// ---- NetGeom (small_step.hpp) + the regions of the packed buffer that only the fp32 kernels have ---------
+template <int F, int Z> struct Net : NetGeom<F, Z> {
+    using G = NetGeom<F, Z>;
+    using G::L;
+    using G::dim;
+    using G::wcount;
+    using G::bf_off;
+    using G::slab_off;
     // packed buffer (float4 units):
-    //   [ Wf(0..7) | Wb(7,6,..,1) | bias frags | E: Wf(0) Wb(1) ]   (+ slack for the ring's pad reads)
-    // Wf = forward fragments, Wb = transposed fragments for the input-gradient chain, packed in the order
-    // the kernels consume them so that every kernel walks ONE linear stream.  Region E duplicates the
-    // two fragment sets of the encoder-gradient kernel (forward 0, then backward 1).
-    __host__ __device__ static constexpr int wcount(int l) { return tiles(dim(l)) * tiles(dim(l + 1)) * 64; }
-    __host__ __device__ static constexpr int wf_off(int l) { int s = 0; for (int j = 0; j < l; ++j) s += wcount(j); return s; }
-    __host__ __device__ static constexpr int wb_off(int l) { int s = wf_off(L); for (int j = L - 1; j > l; --j) s += wcount(j); return s; }
-    __host__ __device__ static constexpr int bf_off(int l) { int s = wb_off(0); for (int j = 0; j < l; ++j) s += tiles(dim(j + 1)) * 4; return s; }
+    //   [ Wf(0..7) | Wb(7,6,..,1) | bias frags | E: Wf(0) Wb(1) | L4 ]   (+ slack for the ring's pad reads)
+    // Region E duplicates the two fragment sets of the encoder-gradient kernel (forward 0, then backward 1).
     __host__ __device__ static constexpr int e_off() { return (bf_off(L) + 63) / 64 * 64; }
     __host__ __device__ static constexpr int ef_off() { return e_off(); }                                             // Wf(0)
     __host__ __device__ static constexpr int eb_off(int l) { return e_off() + wcount(0) + (l < 1 ? wcount(1) : 0); }  // l = 1: Wb(1); l = 0: end of E
@@ -83,14 +74,7 @@ template <int F, int Z> struct Net {
     __host__ __device__ static constexpr int l4_frag_off(int g) { int s = 0; for (int j = 0; j < g; ++j) s += l4_gemm_n(j) * l4_ks(j); return s; }
     __host__ __device__ static constexpr int l4_frags() { return F <= 32 ? l4_frag_off(15) : 0; }      // narrow-input models only
     __host__ __device__ static constexpr int packed_f4() { return l4_off() + l4_frags() + 16 * 64; }
-    // weight-gradient tiles of layer l: tiles(N) x tiles(K + 1) (the extra slot carries db)
-    __host__ __device__ static constexpr int dw_tiles(int l) { return tiles(dim(l + 1)) * tiles(dim(l) + 1); }
-    __host__ __device__ static constexpr int slab_off(int l) { int s = 0; for (int j = 0; j < l; ++j) s += dw_tiles(j); return s; }
     __host__ __device__ static constexpr int slab_f4() { return slab_off(L) * 64 + 4; }  // + loss slot (16 B)
-    // canonical (state-dict) offsets
-    __host__ __device__ static constexpr int w_off(int l) { int s = 0; for (int j = 0; j < l; ++j) s += dim(j + 1) * dim(j) + dim(j + 1); return s; }
-    __host__ __device__ static constexpr int b_off(int l) { return w_off(l) + dim(l + 1) * dim(l); }
-    __host__ __device__ static constexpr int nparams() { return w_off(L); }
 };
 // the packed layout of AE(24, 15) in float4 units: start of region E, end of region E, start of region L4, total
 static_assert(Net<24, 15>::e_off() == 36736 && Net<24, 15>::eb_off(0) == 44224 && Net<24, 15>::l4_off() == 45248 &&
@@ -2971,21 +2955,10 @@ __global__ void __launch_bounds__(512) train_enc_roles_kernel(const v4 *packed, 
 // History (profiles/README.md): the first version kept the images in LDS, formed every [dW | db] tile per workgroup
 // with 4-step MFMAs, wrote a 247-KiB slab per workgroup and reduced the slabs in a second kernel, with an 8-deep
 // fragment ring: 28 + 6 + 5 us per 512-row step against 17 + 6 us now.
-template <class N> struct Lat {
-    __host__ __device__ static constexpr int x_rows(int l) { return 16 * tiles(N::dim(l) + 1); }
-    __host__ __device__ static constexpr int z_rows(int l) { return 16 * tiles(N::dim(l + 1)); }
-    __host__ __device__ static constexpr int x_off(int l) { int s = 0; for (int j = 0; j < l; ++j) s += x_rows(j); return s; }
-    __host__ __device__ static constexpr int z_off(int l) { int s = x_off(N::L); for (int j = 0; j < l; ++j) s += z_rows(j); return s; }
-    static constexpr int xch_f4 = 13 * 64;                       // one exchange buffer: up to 13 tiles
-};
-
-
-template <int NT> __device__ __forceinline__ void lat_collect(const v4 *xch, v4 (&all)[NT], int lane) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) all[t] = xch[t * 64 + lane];
-}
-
-constexpr int kImgStride = 16;   // floats per slot in the global images (= rows per block)
+// The images (StepImages), the fragment sequence (ChainSeq, seq_issue, seq_prologue), collect and the shared parts of the
+// weight-gradient kernel are small_step.hpp's, the same text as the fp64 step's; here is what the f32 MFMA's C/D map and this
+// precision's measured choices make different.
+constexpr int kXchF4 = 13 * 64;                       // one LDS exchange buffer of the 16-row chain: up to 13 tiles
 
 #ifdef BAMD_LAT_TRACE   // debug build: shader-clock stamps of workgroup 0 at every layer boundary (tools/lat_trace.py)
 __device__ unsigned long long g_lat_trace[64];
@@ -2994,38 +2967,6 @@ __device__ unsigned long long g_lat_trace[64];
 #define LAT_T(i) do {} while (0)
 #endif
 
-// The 15 chain GEMMs of one training step as ONE fragment sequence per wave (forward layers 0..7, then the
-// transposed fragments of layers 7..1): a register ring of D fragments runs D fragments AHEAD of the MFMAs across
-// layer boundaries, one refill per consumed fragment, so the loads are spread between the MFMAs.  (Requesting whole
-// layers at once stalls the wave: a 1-KiB fragment load occupies the CU's 64 B/clk L1 path for 16 cycles and a
-// wave issues in order, so 28 loads x 4 waves in a row = 1800 cycles before the first MFMA of the layer.)
-template <class N, int W, int D_> struct LatSeq {
-    static constexpr int D = D_, Wv = W, NG = 15;
-    __host__ __device__ static constexpr int layer(int g) { return g < 8 ? g : 15 - g; }              // 0..7, 7..1
-    __host__ __device__ static constexpr int kd(int g) { return g < 8 ? N::dim(g) : N::dim(layer(g) + 1); }
-    __host__ __device__ static constexpr int nt(int g) { return tiles(g < 8 ? N::dim(g + 1) : N::dim(layer(g))); }
-    __host__ __device__ static constexpr int base(int g) { return (g < 8 ? N::wf_off(g) : N::wb_off(layer(g))) / 64; }
-    __host__ __device__ static constexpr int nl(int g) { return (nt(g) + W - 1) / W; }
-    __host__ __device__ static constexpr int nf(int g) { return tiles(kd(g)) * nl(g); }
-    __host__ __device__ static constexpr int start(int g) { int s = 0; for (int j = 0; j < g; ++j) s += nf(j); return s; }
-    static constexpr int total = start(NG);
-    __host__ __device__ static constexpr int gemm_of(int G) { int g = 0; for (int j = 1; j < NG; ++j) if (G >= start(j)) g = j; return g; }
-};
-// (every index below is a template constant: with loop variables hipcc left the ring in scratch memory)
-template <class SQ, int G>
-__device__ __forceinline__ void seq_issue(v4 (&slot)[SQ::D], const WStream &ws, int wave) {
-    if constexpr (G < SQ::total) {
-        constexpr int g = SQ::gemm_of(G), f = G - SQ::start(g), NL = SQ::nl(g), q = f / NL, i = f % NL, NT = SQ::nt(g);
-        int t = wave + SQ::Wv * i;
-        t = t < NT ? t : NT - 1;
-        slot[G % SQ::D] = frag_rt(ws, SQ::base(g) + q * NT + t);
-    }
-}
-template <class SQ, int... G>
-__device__ __forceinline__ void seq_prologue(v4 (&slot)[SQ::D], const WStream &ws, int wave, std::integer_sequence<int, G...>) {
-    (seq_issue<SQ, G>(slot, ws, wave), ...);
-    __builtin_amdgcn_sched_barrier(0);
-}
 // fragments f and f+1 of GEMM g feed two interleaved accumulators; each consumed fragment is replaced by the one D ahead
 template <class SQ, int g, int f>
 __device__ __forceinline__ void seq_pair(const v4 (&in)[tiles(SQ::kd(g))], v4 (&out)[SQ::nl(g)], v4 (&slot)[SQ::D],
@@ -3085,11 +3026,11 @@ __global__ void __launch_bounds__(64 * W) lat2_chain_kernel(const v4 *packed, co
                                                             const double *__restrict__ feats, float *__restrict__ imgs,
                                                             double *__restrict__ loss_part, int fr, int zr) {
     using N = Net<F, Z>;
-    using LT = Lat<N>;
-    constexpr int kImgFloats = LT::z_off(N::L) * kImgStride;
-    __shared__ __attribute__((aligned(16))) v4 xch_lds[2 * LT::xch_f4 + (N::bf_off(N::L) - N::bf_off(0))];
+    using LT = StepImages<N>;
+    constexpr int kImgFloats = LT::size;
+    __shared__ __attribute__((aligned(16))) v4 xch_lds[2 * kXchF4 + (N::bf_off(N::L) - N::bf_off(0))];
     __shared__ double loss_lds[W];
-    v4 *xchA = xch_lds, *xchB = xchA + LT::xch_f4, *bias_lds = xchB + LT::xch_f4;
+    v4 *xchA = xch_lds, *xchB = xchA + kXchF4, *bias_lds = xchB + kXchF4;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), g = lane >> 4;
     WStream ws = make_stream(packed, N::packed_f4() * 16, lane);
     constexpr int TF = tiles(F), TZ = tiles(Z);
@@ -3100,7 +3041,7 @@ __global__ void __launch_bounds__(64 * W) lat2_chain_kernel(const v4 *packed, co
     const bool valid = row < n;
     RawRows<F> xraw;
     load_rows_issue<F, RT>(xraw, xin, in_f64, row, valid, lane, fr);
-    using SQ = LatSeq<N, W, (W == 4 ? 32 : 24)>;
+    using SQ = ChainSeq<N, W, (W == 4 ? 32 : 24)>;
     v4 ring[SQ::D];
     constexpr int kNB = N::bf_off(N::L) - N::bf_off(0), kBV = (kNB + 64 * W - 1) / (64 * W);
     v4 bv[kBV];                                   // bias fragments: requested with the rows, not after them
@@ -3134,57 +3075,29 @@ __global__ void __launch_bounds__(64 * W) lat2_chain_kernel(const v4 *packed, co
         for (int i = 0; i < LF; ++i) own[i] = a0[(wave + W * i) < TF ? (wave + W * i) : TF - 1];
         lat2_publish<F, true, W>(nullptr, irs, LT::x_off(0), own, lane, wave);
     }
+    // GEMM GI of the sequence on the NIN tiles in exchange buffer XIN -> this wave's tiles SOUT (of NTOUT), from their bias fragments
+#define LAT2_FWD(GI, NIN, XIN, SOUT, NTOUT, ACT)                                                         \
+    {                                                                                                    \
+        v4 ain[NIN]; collect(XIN, ain, lane);                                                            \
+        LAT2_BIAS(SOUT, GI, NTOUT) seq_mm<SQ, GI>(ain, SOUT, ring, ws, wave);                            \
+        if (ACT) lrelu(SOUT);                                                                            \
+    }
+    // own tiles S of a DOUT-feature layer -> exchange buffer XOUT and the image at SLOT; one barrier per layer
+#define LAT2_PUB(DOUT, ONES, XOUT, SLOT, S, TI)                                                          \
+    lat2_publish<DOUT, ONES, W>(XOUT, irs, SLOT, S, lane, wave);                                         \
+    __syncthreads();                                                                                     \
+    LAT_T(TI);
     v4 s1[L13], s2[L7], s3[L4], s4[1], s5[L4], s6[L7], s7[L13], o8[LF];
     LAT2_BIAS(s1, 0, 13) seq_mm<SQ, 0>(a0, s1, ring, ws, wave); lrelu(s1);
-    lat2_publish<200, true, W>(xchA, irs, LT::x_off(1), s1, lane, wave);
-    __syncthreads();
-    LAT_T(2);
-    {
-        v4 a1[13]; lat_collect(xchA, a1, lane);
-        LAT2_BIAS(s2, 1, 7) seq_mm<SQ, 1>(a1, s2, ring, ws, wave); lrelu(s2);
-    }
-    lat2_publish<100, true, W>(xchB, irs, LT::x_off(2), s2, lane, wave);
-    __syncthreads();
-    LAT_T(3);
-    {
-        v4 a2[7]; lat_collect(xchB, a2, lane);
-        LAT2_BIAS(s3, 2, 4) seq_mm<SQ, 2>(a2, s3, ring, ws, wave); lrelu(s3);
-    }
-    lat2_publish<50, true, W>(xchA, irs, LT::x_off(3), s3, lane, wave);
-    __syncthreads();
-    LAT_T(4);
-    {
-        v4 a3[4]; lat_collect(xchA, a3, lane);
-        LAT2_BIAS(s4, 3, TZ) seq_mm<SQ, 3>(a3, s4, ring, ws, wave);                       // en4: no activation
-    }
-    lat2_publish<Z, true, W>(xchB, irs, LT::x_off(4), s4, lane, wave);
-    __syncthreads();
-    LAT_T(5);
-    {
-        v4 a4[TZ]; lat_collect(xchB, a4, lane);
-        LAT2_BIAS(s5, 4, 4) seq_mm<SQ, 4>(a4, s5, ring, ws, wave); lrelu(s5);
-    }
-    lat2_publish<50, true, W>(xchA, irs, LT::x_off(5), s5, lane, wave);
-    __syncthreads();
-    LAT_T(6);
-    {
-        v4 a5[4]; lat_collect(xchA, a5, lane);
-        LAT2_BIAS(s6, 5, 7) seq_mm<SQ, 5>(a5, s6, ring, ws, wave); lrelu(s6);
-    }
-    lat2_publish<100, true, W>(xchB, irs, LT::x_off(6), s6, lane, wave);
-    __syncthreads();
-    LAT_T(7);
-    {
-        v4 a6[7]; lat_collect(xchB, a6, lane);
-        LAT2_BIAS(s7, 6, 13) seq_mm<SQ, 6>(a6, s7, ring, ws, wave); lrelu(s7);
-    }
-    lat2_publish<200, true, W>(xchA, irs, LT::x_off(7), s7, lane, wave);
-    __syncthreads();
-    LAT_T(8);
-    {
-        v4 a7[13]; lat_collect(xchA, a7, lane);
-        LAT2_BIAS(o8, 7, TF) seq_mm<SQ, 7>(a7, o8, ring, ws, wave);                       // de4: no activation
-    }
+    LAT2_PUB(200, true, xchA, LT::x_off(1), s1, 2)
+    LAT2_FWD(1, 13, xchA, s2, 7, true)   LAT2_PUB(100, true, xchB, LT::x_off(2), s2, 3)
+    LAT2_FWD(2, 7, xchB, s3, 4, true)    LAT2_PUB(50, true, xchA, LT::x_off(3), s3, 4)
+    LAT2_FWD(3, 4, xchA, s4, TZ, false)  LAT2_PUB(Z, true, xchB, LT::x_off(4), s4, 5)          // en4: no activation
+    LAT2_FWD(4, TZ, xchB, s5, 4, true)   LAT2_PUB(50, true, xchA, LT::x_off(5), s5, 6)
+    LAT2_FWD(5, 4, xchA, s6, 7, true)    LAT2_PUB(100, true, xchB, LT::x_off(6), s6, 7)
+    LAT2_FWD(6, 7, xchB, s7, 13, true)   LAT2_PUB(200, true, xchA, LT::x_off(7), s7, 8)
+    LAT2_FWD(7, 13, xchA, o8, TF, false)                                                       // de4: no activation
+#undef LAT2_FWD
     // ---------------- loss, dL/drecon ----------------
     double lacc = 0.0;
 #pragma unroll
@@ -3205,76 +3118,26 @@ __global__ void __launch_bounds__(64 * W) lat2_chain_kernel(const v4 *packed, co
         }
     }
     // ---------------- backward chain (input gradients), publishing dZ images ----------------
-    lat2_publish<F, false, W>(xchB, irs, LT::z_off(7), o8, lane, wave);
-    __syncthreads();
-    LAT_T(9);
-    {
-        v4 d8[TF]; lat_collect(xchB, d8, lane);
-        v4 dx[L13]; zero_tiles(dx);
-        seq_mm<SQ, 8>(d8, dx, ring, ws, wave); lrelu_bwd(dx, s7);
-#pragma unroll
-        for (int i = 0; i < L13; ++i) s7[i] = dx[i];          // s7 now holds dZ_6 (own tiles)
+    // input-gradient GEMM GI on the NIN tiles in XIN -> this wave's LOUT tiles, masked by the activations SACT, which they then replace
+#define LAT2_BWD(GI, NIN, LOUT, SACT, XIN, MASK)                                                         \
+    {                                                                                                    \
+        v4 din[NIN]; collect(XIN, din, lane);                                                            \
+        v4 dx[LOUT]; zero_tiles(dx);                                                                     \
+        seq_mm<SQ, GI>(din, dx, ring, ws, wave);                                                         \
+        if (MASK) lrelu_bwd(dx, SACT);                                                                   \
+        _Pragma("unroll") for (int i = 0; i < LOUT; ++i) SACT[i] = dx[i];                                \
     }
-    lat2_publish<200, false, W>(xchA, irs, LT::z_off(6), s7, lane, wave);
-    __syncthreads();
-    LAT_T(10);
-    {
-        v4 d7[13]; lat_collect(xchA, d7, lane);
-        v4 dx[L7]; zero_tiles(dx);
-        seq_mm<SQ, 9>(d7, dx, ring, ws, wave); lrelu_bwd(dx, s6);
-#pragma unroll
-        for (int i = 0; i < L7; ++i) s6[i] = dx[i];
-    }
-    lat2_publish<100, false, W>(xchB, irs, LT::z_off(5), s6, lane, wave);
-    __syncthreads();
-    LAT_T(11);
-    {
-        v4 d6[7]; lat_collect(xchB, d6, lane);
-        v4 dx[L4]; zero_tiles(dx);
-        seq_mm<SQ, 10>(d6, dx, ring, ws, wave); lrelu_bwd(dx, s5);
-#pragma unroll
-        for (int i = 0; i < L4; ++i) s5[i] = dx[i];
-    }
-    lat2_publish<50, false, W>(xchA, irs, LT::z_off(4), s5, lane, wave);
-    __syncthreads();
-    LAT_T(12);
-    {
-        v4 d5[4]; lat_collect(xchA, d5, lane);
-        v4 dx[1]; zero_tiles(dx);
-        seq_mm<SQ, 11>(d5, dx, ring, ws, wave);                                            // dL/dz: en4 has no activation
-        s4[0] = dx[0];
-    }
-    lat2_publish<Z, false, W>(xchB, irs, LT::z_off(3), s4, lane, wave);
-    __syncthreads();
-    LAT_T(13);
-    {
-        v4 d4[TZ]; lat_collect(xchB, d4, lane);
-        v4 dx[L4]; zero_tiles(dx);
-        seq_mm<SQ, 12>(d4, dx, ring, ws, wave); lrelu_bwd(dx, s3);
-#pragma unroll
-        for (int i = 0; i < L4; ++i) s3[i] = dx[i];
-    }
-    lat2_publish<50, false, W>(xchA, irs, LT::z_off(2), s3, lane, wave);
-    __syncthreads();
-    LAT_T(14);
-    {
-        v4 d3[4]; lat_collect(xchA, d3, lane);
-        v4 dx[L7]; zero_tiles(dx);
-        seq_mm<SQ, 13>(d3, dx, ring, ws, wave); lrelu_bwd(dx, s2);
-#pragma unroll
-        for (int i = 0; i < L7; ++i) s2[i] = dx[i];
-    }
-    lat2_publish<100, false, W>(xchB, irs, LT::z_off(1), s2, lane, wave);
-    __syncthreads();
-    LAT_T(15);
-    {
-        v4 d2[7]; lat_collect(xchB, d2, lane);
-        v4 dx[L13]; zero_tiles(dx);
-        seq_mm<SQ, 14>(d2, dx, ring, ws, wave); lrelu_bwd(dx, s1);
-#pragma unroll
-        for (int i = 0; i < L13; ++i) s1[i] = dx[i];
-    }
+    LAT2_PUB(F, false, xchB, LT::z_off(7), o8, 9)
+    LAT2_BWD(8, TF, L13, s7, xchB, true)   LAT2_PUB(200, false, xchA, LT::z_off(6), s7, 10)     // s7 now holds dZ_6 (own tiles)
+    LAT2_BWD(9, 13, L7, s6, xchA, true)    LAT2_PUB(100, false, xchB, LT::z_off(5), s6, 11)
+    LAT2_BWD(10, 7, L4, s5, xchB, true)    LAT2_PUB(50, false, xchA, LT::z_off(4), s5, 12)
+    LAT2_BWD(11, 4, 1, s4, xchA, false)    LAT2_PUB(Z, false, xchB, LT::z_off(3), s4, 13)       // dL/dz: en4 has no activation
+    LAT2_BWD(12, TZ, L4, s3, xchB, true)   LAT2_PUB(50, false, xchA, LT::z_off(2), s3, 14)
+    LAT2_BWD(13, 4, L7, s2, xchA, true)    LAT2_PUB(100, false, xchB, LT::z_off(1), s2, 15)
+    LAT2_BWD(14, 7, L13, s1, xchB, true)
     lat2_publish<200, false, W>(nullptr, irs, LT::z_off(0), s1, lane, wave);
+#undef LAT2_BWD
+#undef LAT2_PUB
 #undef LAT2_BIAS
     // loss partial of this 16-row block: lanes of a wave, then waves 0..W-1 (fixed order)
 #pragma unroll
@@ -3405,8 +3268,8 @@ __global__ void __launch_bounds__(256) lat4_chain_kernel(const v4 *__restrict__ 
                                                          double *__restrict__ loss_part, int fr, int zr) {
     using N = Net<F, Z>;
     using T = L4<N>;
-    using LT = Lat<N>;
-    constexpr int kImgFloats = LT::z_off(N::L) * kImgStride;
+    using LT = StepImages<N>;
+    constexpr int kImgFloats = LT::size;
     // every feature slot a GEMM reads (4 x steps <= 64 x groups) is written by the producing epilogue: no zero fill needed
     __shared__ __attribute__((aligned(16))) float lds[T::lds_floats];
     __shared__ double loss_lds[4];
@@ -3580,19 +3443,12 @@ __global__ void __launch_bounds__(256) lat4_chain_kernel(const v4 *__restrict__ 
     if (threadIdx.x == 0) loss_part[4 * blk + quad] = ((loss_lds[0] + loss_lds[1]) + loss_lds[2]) + loss_lds[3];
 }
 
-struct AdamArgs {   // where the state of one Adam step lives, and its scalars
-    float *params, *pcopy, *m, *v, *packed;
-    const int *sc_off, *sc_idx;
-    double *loss_accum;
-    AdamScalars s;
-};
+using AdamArgs = AdamTargets<float>;
 
-// grid = 8 x ceil((dW tiles + 1) / 8).  A block contracts dZ^T (tile nt of layer l) with X (tile kt) over all 16-row
-// blocks.  Workgroups are dealt to the 8 XCDs round-robin and every XCD has its own L2, so XCD c takes the CONTIGUOUS
-// tile range [c * per, (c + 1) * per): neighbouring tiles share their X / dZ image slices, each slice then crosses the
-// fabric into (about) one L2 instead of eight.  The map entry and the optimiser state of the thread's parameter are
-// requested BEFORE the image loop, so the dependent global round trips overlap instead of queueing up.
-enum { DW_WRITE = 0, DW_ADAM = 1, DW_ACCUM = 2 };   // grads = g | Adam on g (+ grads = g) | grads += g
+// A block contracts dZ^T (tile nt of layer l) with X (tile kt) over all 16-row blocks.  The tile map (one contiguous tile range per
+// XCD), the loss tile, the four-wave sum and the Adam finish are small_step.hpp's; this kernel's own: the block ranges (phases 1 / 2),
+// DW_ACCUM, the point at which it requests the scatter slots, and the tile decode (below).  The map entry and the optimiser state of
+// the thread's parameter are requested BEFORE the image loop, so the dependent global round trips overlap instead of queueing up.
 template <class N, int MODE>
 __global__ void __launch_bounds__(256) lat2_dw_kernel(const float *__restrict__ imgs, int nblk, const double *__restrict__ loss_part, int nloss,
                                                       const int *__restrict__ inv_map, float *__restrict__ grads, AdamArgs ad,
@@ -3604,22 +3460,14 @@ __global__ void __launch_bounds__(256) lat2_dw_kernel(const float *__restrict__ 
     // adds them in range order and finishes (Adam / store / accumulate).  Measured us per step, split / one launch: 8192 rows
     // 64.8 / 69.6, 12288 rows 90.5 / 99.8; at 4096 rows 43.8 / 44.2 and below that the second launch costs more than it saves:
     // there the kernel is bound by the 153 MB the 298 tiles read from the images (each slice is shared by 7-13 tiles), not by latency.
-    using LT = Lat<N>;
-    constexpr int kImgFloats = LT::z_off(N::L) * kImgStride, T = N::slab_off(N::L);
-    constexpr int kPerXcd = (T + 1 + 7) / 8;
+    using LT = StepImages<N>;
+    constexpr int kImgFloats = LT::size, T = N::slab_off(N::L);
     __shared__ __attribute__((aligned(16))) v4 red[4 * 64];
-    const int tile = (blockIdx.x & 7) * kPerXcd + (blockIdx.x >> 3);
+    const int tile = dw_tile_of_block<N>();
     if (tile > T) return;
     if (tile == T && phase == 1) return;
-    if (tile == T) {   // loss: fixed-order sum of the per-block partials, / C
-        // 256 strided sums, then a fixed tree (ONE thread adding 32 .. 128 partials one dependent L2 round trip after the other
-        // was the longest workgroup of this kernel: 6.5 us of its 6.5-9 us)
-        const double s = block_sum_fixed(loss_part, nloss, (double *)red);
-        if (threadIdx.x == 0) {
-            const float gl = (float)(s * inv_c);
-            if (grads) grads[np] = MODE == DW_ACCUM ? grads[np] + gl : gl;
-            if (MODE == DW_ADAM && ad.loss_accum) *ad.loss_accum += (double)gl;
-        }
+    if (tile == T) {
+        dw_loss_tile<MODE>(loss_part, nloss, inv_c, grads, np, ad.loss_accum, (double *)red);
         return;
     }
 #ifdef BAMD_LAT_TRACE
@@ -3629,6 +3477,9 @@ __global__ void __launch_bounds__(256) lat2_dw_kernel(const float *__restrict__ 
 #endif
     DW_T(0);
     const int p = inv_map[tile * 256 + threadIdx.x];
+    // the tile decode is this kernel's own text (= dw_tile_decode of small_step.hpp, which dw64_kernel calls): through the function the
+    // kernel came out one instruction shorter with other SGPR numbers, and the 4,096-row step with Adam measured 44.1-44.4 -> 45.5-45.7 us
+    // in both handle orders (profiles/small_step_one_text.txt); with this text the WRITE and ACCUM instantiations are the parent's code
     int l = 0;
 #pragma unroll
     for (int j = 1; j < N::L; ++j) if (tile >= N::slab_off(j)) l = j;
@@ -3638,8 +3489,8 @@ __global__ void __launch_bounds__(256) lat2_dw_kernel(const float *__restrict__ 
         if (l == j) { nt_count = tiles(N::dim(j + 1)); soff = N::slab_off(j); xo = LT::x_off(j); zo = LT::z_off(j); }
     const int idx = tile - soff, kt = idx / nt_count, nt = idx - kt * nt_count;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, i = lane & 15;
-    const float *pz = imgs + ((zo + 16 * nt + i) * kImgStride + 4 * g);
-    const float *px = imgs + ((xo + 16 * kt + i) * kImgStride + 4 * g);
+    const float *pz = imgs + ((zo + 16 * nt + i) * LT::stride + 4 * g);
+    const float *px = imgs + ((xo + 16 * kt + i) * LT::stride + 4 * g);
     float pm = 0.f, pv = 0.f, pp = 0.f;
     int s0 = 0, s1 = 0;
     if (MODE == DW_ADAM && p >= 0) { pm = ad.m[p]; pv = ad.v[p]; pp = ad.params[p]; s0 = ad.sc_off[p]; s1 = ad.sc_off[p + 1]; }
@@ -3665,15 +3516,12 @@ __global__ void __launch_bounds__(256) lat2_dw_kernel(const float *__restrict__ 
     DW_T(2);
     red[wave * 64 + lane] = acc;
     int sidx[4] = {-1, -1, -1, -1};                                  // packed copies of this parameter (forward, transposed, region E)
-    if (MODE == DW_ADAM && p >= 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (s0 + k < s1) sidx[k] = ad.sc_idx[s0 + k];
-    }
+    if (MODE == DW_ADAM && p >= 0) dw_adam_slots(ad, s0, s1, sidx);
     __syncthreads();
     DW_T(3);
     const float *rf = (const float *)red;
     const int e = threadIdx.x;
-    float gsum = ((rf[e] + rf[256 + e]) + rf[512 + e]) + rf[768 + e];
+    float gsum = dw_sum4(rf, e);
     if (phase == 1) { part[((int64_t)tile * nsplit + blockIdx.y) * 256 + e] = gsum; return; }
     if (phase == 2) {
         gsum = 0.f;
@@ -3681,16 +3529,7 @@ __global__ void __launch_bounds__(256) lat2_dw_kernel(const float *__restrict__ 
     }
     if (p < 0) return;
     if (grads) grads[p] = MODE == DW_ACCUM ? grads[p] + gsum : gsum;
-    if (MODE == DW_ADAM) {   // on the 256 parameters this tile owns
-        const float pn = adam_update(ad.s, gsum, pm, pv, pp);
-        ad.m[p] = pm;
-        ad.v[p] = pv;
-        ad.params[p] = pn;
-        if (ad.pcopy) ad.pcopy[p] = pn;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (sidx[k] >= 0) ad.packed[sidx[k]] = pn;
-        for (int k = s0 + 4; k < s1; ++k) ad.packed[ad.sc_idx[k]] = pn;
-    }
+    if (MODE == DW_ADAM) dw_adam_finish(ad, p, gsum, pm, pv, pp, sidx, s0, s1);   // on the 256 parameters this tile owns
     DW_T(4);
 }
 
@@ -3773,6 +3612,10 @@ struct FusedState {
     bool tail_split = true;            // short remainder of the persistent loop on the small-batch kernels (BALER_AMD_TAIL_SPLIT=0: off)
 };
 
+struct Slots32 {      // slot_feature on the A-operand row i (as lane group i / 4, register i % 4) and on register r of lane group g
+    static int row(int d, int t, int i) { return slot_feature(d, t, i / 4, i % 4); }
+    static int reg(int d, int t, int g, int r) { return slot_feature(d, t, g, r); }
+};
 template <int F, int Z, bool TRAIN>
 static int build_maps(bamd_handle *h, FusedState *st) {
     // Geometry (tiles, fragment order, slot -> feature) from the instantiated Net<F, Z>; which slots hold a parameter, and the
@@ -3786,37 +3629,12 @@ static int build_maps(bamd_handle *h, FusedState *st) {
     auto b_off_r = [&](int l) { return (int)h->b_off[l]; };
     std::vector<int> src((size_t)N::packed_f4() * 4, -1);
     std::vector<int> smap((size_t)nparams_r, -1);
-    for (int l = 0; l < N::L; ++l) {
-        const int K = N::dim(l), NN = N::dim(l + 1), KT = tiles(K), NT = tiles(NN);
+    // forward frags [q][t][lane].comp[r] = W[n(t, i = lane & 15)][k(q, g = lane >> 4, r)], backward frags (layers 1..7)
+    // [tq][tk][lane].comp[r] = W[n(tq, g, r)][k(tk, i)], bias frags [t][g].comp[r] = b[n(t, g, r)]
+    fill_fragment_maps<N>(src, h, Slots32{});
+    for (int l = 0; l < N::L && TRAIN; ++l) {
+        const int K = N::dim(l), NN = N::dim(l + 1), NT = tiles(NN);
         const int Kr = dim_r(l), NNr = dim_r(l + 1);
-        // forward frags: [q][t][lane].comp[r] = W[n(t, i = lane & 15)][k(q, g = lane >> 4, r)]
-        for (int q = 0; q < KT; ++q)
-            for (int t = 0; t < NT; ++t)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        int i = lane & 15, g = lane >> 4;
-                        int nf = slot_feature(NN, t, i / 4, i % 4), kf = slot_feature(K, q, g, r);
-                        if (nf >= 0 && kf >= 0 && nf < NNr && kf < Kr)
-                            src[((size_t)N::wf_off(l) + (q * NT + t) * 64 + lane) * 4 + r] = w_off_r(l) + nf * Kr + kf;
-                    }
-        // backward frags (layers 1..7): [tq][tk][lane].comp[r] = W[n(tq, g, r)][k(tk, i)]
-        for (int tq = 0; tq < NT && l >= 1; ++tq)
-            for (int tk = 0; tk < KT; ++tk)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        int i = lane & 15, g = lane >> 4;
-                        int nf = slot_feature(NN, tq, g, r), kf = slot_feature(K, tk, i / 4, i % 4);
-                        if (nf >= 0 && kf >= 0 && nf < NNr && kf < Kr)
-                            src[((size_t)N::wb_off(l) + (tq * KT + tk) * 64 + lane) * 4 + r] = w_off_r(l) + nf * Kr + kf;
-                    }
-        // bias frags: [t][g].comp[r] = b[n(t, g, r)]
-        for (int t = 0; t < NT; ++t)
-            for (int g = 0; g < 4; ++g)
-                for (int r = 0; r < 4; ++r) {
-                    int nf = slot_feature(NN, t, g, r);
-                    if (nf >= 0 && nf < NNr) src[((size_t)N::bf_off(l) + t * 4 + g) * 4 + r] = b_off_r(l) + nf;
-                }
-        if (!TRAIN) continue;
         // slab map: tile idx = kt*NT + nt; lane (j = lane & 15 -> k slot row 16kt + j), reg r -> n slot row 4g + r
         const int KTp = tiles(K + 1);
         const int T1 = tiles(K) - 1, V = K - 16 * T1, ones_row = 16 * T1 + 4 * (V % 4) + (V / 4);
@@ -3865,12 +3683,8 @@ static int build_maps(bamd_handle *h, FusedState *st) {
         smap.swap(inv);
     }
     {   // inverse of the pack map: for every parameter the list of packed positions that hold a copy of it
-        std::vector<int> off((size_t)nparams_r + 1, 0), idx;
-        for (int v : src) if (v >= 0) off[v + 1]++;
-        for (int p = 0; p < nparams_r; ++p) off[p + 1] += off[p];
-        idx.resize(off[nparams_r]);
-        std::vector<int> cur(off.begin(), off.end() - 1);
-        for (size_t i = 0; i < src.size(); ++i) if (src[i] >= 0) idx[cur[src[i]]++] = (int)i;
+        std::vector<int> off, idx;
+        invert_pack_map(src, nparams_r, off, idx);
         int rc2 = st->sc_off.ensure(off.size() * sizeof(int));
         if (rc2) return rc2;
         rc2 = st->sc_idx.ensure(idx.size() * sizeof(int));
@@ -4041,7 +3855,7 @@ template <int F, int Z, bool RT = false> struct Impl {
                            const AdamArgs *ad, hipStream_t s, bool accumulate = false) {
         FusedState *st = state_of(h);
         const int nblk = (int)((n + 15) / 16);
-        constexpr size_t img_bytes = (size_t)Lat<N>::z_off(N::L) * kImgStride * sizeof(float);
+        constexpr size_t img_bytes = (size_t)StepImages<N>::size * sizeof(float);
         int rc = st->imgs.ensure(img_bytes * (size_t)nblk);
         if (rc) return rc;
         rc = h->lossp.ensure(sizeof(double) * (size_t)(4 * nblk > 1024 ? 4 * nblk : 1024));
@@ -4063,7 +3877,7 @@ template <int F, int Z, bool RT = false> struct Impl {
             // 4 waves per workgroup: a CU has four MFMA units, 8 waves (2 per SIMD) measured no faster (23.4 vs 23.3 us per step)
             hipLaunchKernelGGL((lat2_chain_kernel<F, Z, 4, RT>), dim3(nblk), dim3(256), 0, s, (const v4 *)h->packed.p, x,
                                x_dtype == BAMD_F64, n, features, (float *)st->imgs.p, (double *)h->lossp.p, fr(h), zr(h));
-        const dim3 grid(8 * ((N::slab_off(N::L) + 1 + 7) / 8));
+        const dim3 grid(dw_tile_grid<N>());
         // tiles x block ranges from 8192 rows on (see lat2_dw_kernel)
         const int nsplit = nblk >= 512 ? 4 : 1;
         float *part = nullptr;
@@ -4870,12 +4684,7 @@ static int train_step_on(bamd_handle *h, const void *x, int x_dtype, int64_t n, 
                          void *params, void *m, void *v, const bamd_adam &hp, double *loss_accum, hipStream_t s) {
     if (!state_of(h)->ops->train_step) return BAMD_ERR_UNSUPPORTED;
     FusedState *st = state_of(h);
-    AdamArgs ad;
-    ad.params = (float *)params; ad.pcopy = (float *)h->params.p; ad.m = (float *)m; ad.v = (float *)v;
-    ad.packed = (float *)h->packed.p;
-    ad.sc_off = (const int *)st->sc_off.p; ad.sc_idx = (const int *)st->sc_idx.p;
-    ad.loss_accum = loss_accum;
-    ad.s = adam_scalars(hp);
+    const AdamArgs ad = adam_targets<float>(h, params, m, v, h->packed.p, st->sc_off.p, st->sc_idx.p, loss_accum, hp);
     return st->ops->train_step(h, x, x_dtype, n, features, grads, ad, s);
 }
 

@@ -1,9 +1,11 @@
 // fp64 small-batch training step of AE(F, Z) on v_mfma_f64_16x16x4_f64 (BAMD_MODE_F64): the reference's own dtype
-// (models.py:128-136) at the reference's batch size -- the mode that pins 500-step CLI runs at 1e-9.  Same two-launch
-// structure as the fp32 small-batch step in fused.hip (a workgroup owns ONE 16-row block and its 4 waves split every
+// (models.py:128-136) at the reference's batch size -- the mode that pins 500-step CLI runs at 1e-9.  The two-launch
+// structure of the fp32 small-batch step in fused.hip (a workgroup owns ONE 16-row block and its 4 waves split every
 // layer's output tiles, swapping tiles through a double-buffered LDS exchange; then one workgroup per weight-gradient
-// tile over the whole batch, optionally fused with Adam and the refresh of the packed weights), re-derived for the
-// f64 MFMA, whose C/D map is NOT the f32 one:
+// tile over the whole batch, optionally fused with Adam and the refresh of the packed weights).  What the two precisions
+// share is written once, in small_step.hpp: the geometry, the images, the fragment sequence, the tile map / decode / loss
+// tile / four-wave sum / Adam finish of the weight-gradient kernel, the fragment and scatter maps.  What is here is what
+// the f64 MFMA makes different; its C/D map is NOT the f32 one:
 //     f32 16x16x4:  D row = 4 (lane >> 4) + reg        f64 16x16x4:  D row = (lane >> 4) + 4 reg
 // so register r of an output tile on lane group g holds feature 16 t + 4 r + g, and -- because the B operand of MFMA
 // step r takes k = g from lane group g -- step r of the next layer consumes exactly features 16 q + 4 r .. + 3: the chain
@@ -30,34 +32,8 @@ namespace {
 #ifdef BAMD_Q4_TRACE   // debug build: shader-clock stamps of one dw64_kernel workgroup (tools/q4_trace.py)
 __device__ unsigned long long g_dw64_trace[8];
 #endif
-// The 15 chain GEMMs of one step as ONE fragment sequence per wave (forward layers 0..7, then the transposed fragments
-// of layers 7..1); a register ring runs D fragments ahead of the MFMAs across layer boundaries (see fused.hip LatSeq).
-template <class N, int W, int D_> struct Seq {
-    static constexpr int D = D_, Wv = W, NG = 15;
-    __host__ __device__ static constexpr int layer(int g) { return g < 8 ? g : 15 - g; }
-    __host__ __device__ static constexpr int kd(int g) { return g < 8 ? N::dim(g) : N::dim(layer(g) + 1); }
-    __host__ __device__ static constexpr int nt(int g) { return tiles(g < 8 ? N::dim(g + 1) : N::dim(layer(g))); }
-    __host__ __device__ static constexpr int base(int g) { return (g < 8 ? N::wf_off(g) : N::wb_off(layer(g))) / 64; }
-    __host__ __device__ static constexpr int nl(int g) { return (nt(g) + W - 1) / W; }
-    __host__ __device__ static constexpr int nf(int g) { return tiles(kd(g)) * nl(g); }
-    __host__ __device__ static constexpr int start(int g) { int s = 0; for (int j = 0; j < g; ++j) s += nf(j); return s; }
-    static constexpr int total = start(NG);
-    __host__ __device__ static constexpr int gemm_of(int G) { int g = 0; for (int j = 1; j < NG; ++j) if (G >= start(j)) g = j; return g; }
-};
-template <class SQ, int G>
-__device__ __forceinline__ void seq_issue(d4 (&slot)[SQ::D], const WStream &ws, int wave) {
-    if constexpr (G < SQ::total) {
-        constexpr int g = SQ::gemm_of(G), f = G - SQ::start(g), NL = SQ::nl(g), q = f / NL, i = f % NL, NT = SQ::nt(g);
-        int t = wave + SQ::Wv * i;
-        t = t < NT ? t : NT - 1;
-        slot[G % SQ::D] = frag_rt(ws, SQ::base(g) + q * NT + t);
-    }
-}
-template <class SQ, int... G>
-__device__ __forceinline__ void seq_prologue(d4 (&slot)[SQ::D], const WStream &ws, int wave, std::integer_sequence<int, G...>) {
-    (seq_issue<SQ, G>(slot, ws, wave), ...);
-    __builtin_amdgcn_sched_barrier(0);
-}
+// The 15 chain GEMMs of one step are ONE fragment sequence per wave: ChainSeq, seq_issue and seq_prologue of small_step.hpp, on this
+// file's d4 and WStream.  Here: how a fragment of the sequence feeds the f64 MFMA (one accumulator; fp32 interleaves two, fused.hip seq_pair).
 template <class SQ, int g, int f>
 __device__ __forceinline__ void seq_one(const d4 (&in)[tiles(SQ::kd(g))], d4 (&out)[SQ::nl(g)], d4 (&slot)[SQ::D], const WStream &ws,
                                         int wave) {
@@ -79,10 +55,6 @@ __device__ __forceinline__ void seq_mm(const d4 (&in)[tiles(SQ::kd(g))], d4 (&ou
     seq_mm_impl<SQ, g>(in, out, slot, ws, wave, std::make_integer_sequence<int, SQ::nf(g)>{});
 }
 
-template <int NT> __device__ __forceinline__ void collect(const d4 *xch, d4 (&all)[NT], int lane) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) all[t] = xch[t * 64 + lane];
-}
 template <int NL> __device__ __forceinline__ void lrelu_bwd(d4 (&d)[NL], const d4 (&y)[NL]) {
 #pragma unroll
     for (int i = 0; i < NL; ++i)
@@ -106,7 +78,7 @@ __device__ __forceinline__ void publish(d4 *xch, double *img, int slot0, const d
             for (int r = 0; r < 4; ++r) {
                 double v = loc[i][r];
                 if (ONES && t == T1 && g + 4 * r == V) v = 1.0;
-                img[(slot0 + 16 * t + g + 4 * r) * 16 + col] = v;
+                img[(slot0 + 16 * t + g + 4 * r) * kImgStride + col] = v;
             }
         }
     }
@@ -117,6 +89,7 @@ __global__ void __launch_bounds__(64 * W) chain64_kernel(const d4 *packed, const
                                                          const double *__restrict__ feats, double *__restrict__ imgs,
                                                          double *__restrict__ loss_part, int fr) {
     using N = Net64<F, Z>;
+    using IM = StepImages<N>;
     constexpr int TF = tiles(F), TZ = tiles(Z);
     static_assert(TF <= W && TZ <= W && F % 16 != 0, "input / latent tiles");
     constexpr int kNB = N::bf_off(N::L) - N::bf_off(0);
@@ -144,12 +117,12 @@ __global__ void __launch_bounds__(64 * W) chain64_kernel(const d4 *packed, const
             if (feats) v = (v - feats[fc]) / feats[fw + fc];
             a0[t][r] = live ? v : 0.0;
         }
-    using SQ = Seq<N, W, 12>;
+    using SQ = ChainSeq<N, W, 12>;
     d4 ring[SQ::D];
     for (int i = threadIdx.x; i < kNB; i += 64 * W) bias_lds[i] = packed[N::bf_off(0) + i];
     seq_prologue<SQ>(ring, ws, wave, std::make_integer_sequence<int, SQ::D>{});
     __syncthreads();
-    double *img = imgs + (int64_t)blockIdx.x * N::img_doubles;
+    double *img = imgs + (int64_t)blockIdx.x * IM::size;
 #define BIAS64(loc, l, NTl)                                                                              \
     _Pragma("unroll") for (int i = 0; i < (NTl + W - 1) / W; ++i) {                                      \
         int t_ = wave + W * i; t_ = t_ < NTl ? t_ : NTl - 1;                                             \
@@ -161,29 +134,29 @@ __global__ void __launch_bounds__(64 * W) chain64_kernel(const d4 *packed, const
     {
         d4 own[LF];
         own[0] = a0[wave < TF ? wave : TF - 1];
-        publish<F, true, W>(nullptr, img, N::x_off(0), own, lane, wave);
+        publish<F, true, W>(nullptr, img, IM::x_off(0), own, lane, wave);
     }
     d4 s1[L13], s2[L7], s3[L4], s4[1], s5[L4], s6[L7], s7[L13], o8[LF];
     BIAS64(s1, 0, 13) seq_mm<SQ, 0>(a0, s1, ring, ws, wave); lrelu(s1);
-    publish<200, true, W>(xchA, img, N::x_off(1), s1, lane, wave);
+    publish<200, true, W>(xchA, img, IM::x_off(1), s1, lane, wave);
     __syncthreads();
     { d4 a1[13]; collect(xchA, a1, lane); BIAS64(s2, 1, 7) seq_mm<SQ, 1>(a1, s2, ring, ws, wave); lrelu(s2); }
-    publish<100, true, W>(xchB, img, N::x_off(2), s2, lane, wave);
+    publish<100, true, W>(xchB, img, IM::x_off(2), s2, lane, wave);
     __syncthreads();
     { d4 a2[7]; collect(xchB, a2, lane); BIAS64(s3, 2, 4) seq_mm<SQ, 2>(a2, s3, ring, ws, wave); lrelu(s3); }
-    publish<50, true, W>(xchA, img, N::x_off(3), s3, lane, wave);
+    publish<50, true, W>(xchA, img, IM::x_off(3), s3, lane, wave);
     __syncthreads();
     { d4 a3[4]; collect(xchA, a3, lane); BIAS64(s4, 3, TZ) seq_mm<SQ, 3>(a3, s4, ring, ws, wave); }          // en4: no activation
-    publish<Z, true, W>(xchB, img, N::x_off(4), s4, lane, wave);
+    publish<Z, true, W>(xchB, img, IM::x_off(4), s4, lane, wave);
     __syncthreads();
     { d4 a4[TZ]; collect(xchB, a4, lane); BIAS64(s5, 4, 4) seq_mm<SQ, 4>(a4, s5, ring, ws, wave); lrelu(s5); }
-    publish<50, true, W>(xchA, img, N::x_off(5), s5, lane, wave);
+    publish<50, true, W>(xchA, img, IM::x_off(5), s5, lane, wave);
     __syncthreads();
     { d4 a5[4]; collect(xchA, a5, lane); BIAS64(s6, 5, 7) seq_mm<SQ, 5>(a5, s6, ring, ws, wave); lrelu(s6); }
-    publish<100, true, W>(xchB, img, N::x_off(6), s6, lane, wave);
+    publish<100, true, W>(xchB, img, IM::x_off(6), s6, lane, wave);
     __syncthreads();
     { d4 a6[7]; collect(xchB, a6, lane); BIAS64(s7, 6, 13) seq_mm<SQ, 6>(a6, s7, ring, ws, wave); lrelu(s7); }
-    publish<200, true, W>(xchA, img, N::x_off(7), s7, lane, wave);
+    publish<200, true, W>(xchA, img, IM::x_off(7), s7, lane, wave);
     __syncthreads();
     { d4 a7[13]; collect(xchA, a7, lane); BIAS64(o8, 7, TF) seq_mm<SQ, 7>(a7, o8, ring, ws, wave); }         // de4: no activation
 #undef BIAS64
@@ -201,7 +174,7 @@ __global__ void __launch_bounds__(64 * W) chain64_kernel(const d4 *packed, const
         }
     }
     // ---------------- backward chain (input gradients), publishing dZ images ----------------
-    publish<F, false, W>(xchB, img, N::z_off(7), o8, lane, wave);
+    publish<F, false, W>(xchB, img, IM::z_off(7), o8, lane, wave);
     __syncthreads();
 #define BWD64(GI, NIN, LOUT, SACT, XIN, XOUT, ZO, DOUT, MASK)                                            \
     {                                                                                                    \
@@ -214,13 +187,13 @@ __global__ void __launch_bounds__(64 * W) chain64_kernel(const d4 *packed, const
     }                                                                                                    \
     publish<DOUT, false, W>(XOUT, img, ZO, SACT, lane, wave);                                            \
     __syncthreads();
-    BWD64(8, TF, L13, s7, xchB, xchA, N::z_off(6), 200, true)
-    BWD64(9, 13, L7, s6, xchA, xchB, N::z_off(5), 100, true)
-    BWD64(10, 7, L4, s5, xchB, xchA, N::z_off(4), 50, true)
-    BWD64(11, 4, 1, s4, xchA, xchB, N::z_off(3), Z, false)                 // dL/dz: en4 has no activation
-    BWD64(12, TZ, L4, s3, xchB, xchA, N::z_off(2), 50, true)
-    BWD64(13, 4, L7, s2, xchA, xchB, N::z_off(1), 100, true)
-    BWD64(14, 7, L13, s1, xchB, (d4 *)nullptr, N::z_off(0), 200, true)
+    BWD64(8, TF, L13, s7, xchB, xchA, IM::z_off(6), 200, true)
+    BWD64(9, 13, L7, s6, xchA, xchB, IM::z_off(5), 100, true)
+    BWD64(10, 7, L4, s5, xchB, xchA, IM::z_off(4), 50, true)
+    BWD64(11, 4, 1, s4, xchA, xchB, IM::z_off(3), Z, false)                 // dL/dz: en4 has no activation
+    BWD64(12, TZ, L4, s3, xchB, xchA, IM::z_off(2), 50, true)
+    BWD64(13, 4, L7, s2, xchA, xchB, IM::z_off(1), 100, true)
+    BWD64(14, 7, L13, s1, xchB, (d4 *)nullptr, IM::z_off(0), 200, true)
 #undef BWD64
     // loss partial of this 16-row block: lanes of a wave, then waves 0..W-1 (fixed order)
 #pragma unroll
@@ -239,7 +212,7 @@ __global__ void __launch_bounds__(64 * W) chain64_kernel(const d4 *packed, const
 // chain64_kernel gives a block to a whole workgroup (4 waves split every layer's tiles and swap them through LDS, one barrier per
 // layer): right for the 512-row step, but at 262,144 rows it spends 1.6 ms at 55 % MFMA busy -- 15 barriers per block, and every
 // block's workgroup streams the whole model.  infer64_kernel shows what the fp64 MFMA does when a wave owns all tiles of its rows
-// (85-89 % busy).  This is that formulation for training: Seq<N, 1, D> is the 15-GEMM fragment sequence of ONE wave (forward 0..7,
+// (85-89 % busy).  This is that formulation for training: ChainSeq<N, 1, D> is the 15-GEMM fragment sequence of ONE wave (forward 0..7,
 // then the transposed fragments of layers 7..1), a layer's output tiles are the next GEMM's B operand as they stand, nothing is
 // exchanged, no barrier after the bias fragments are staged.  The images ([slot][16 rows], global) are written exactly as
 // chain64_kernel writes them -- same values bit for bit: every output element still accumulates its k blocks in order -- so the
@@ -267,6 +240,7 @@ __global__ void __launch_bounds__(256) chain64r_kernel(const d4 *packed, const v
                                                        const double *__restrict__ feats, double *__restrict__ imgs,
                                                        double *__restrict__ loss_part, int nblk, int fr) {
     using N = Net64<F, Z>;
+    using IM = StepImages<N>;
     constexpr int TF = tiles(F), TZ = tiles(Z);
     static_assert(TZ <= 2 && F % 16 != 0, "input / latent tiles");
     constexpr int kNB = N::bf_off(N::L) - N::bf_off(0);
@@ -296,16 +270,16 @@ __global__ void __launch_bounds__(256) chain64r_kernel(const d4 *packed, const v
             if (feats) v = (v - feats[fc]) / feats[fw + fc];
             a0[t][r] = live ? v : 0.0;
         }
-    using SQ = Seq<N, 1, 8>;
+    using SQ = ChainSeq<N, 1, 8>;
     d4 ring[SQ::D];
     seq_prologue<SQ>(ring, ws, 0, std::make_integer_sequence<int, SQ::D>{});
-    double *img = imgs + (int64_t)blk * N::img_doubles;
+    double *img = imgs + (int64_t)blk * IM::size;
 #define BIAS64R(loc, l, NTl)                                                                             \
     _Pragma("unroll") for (int i = 0; i < NTl; ++i) loc[i] = bias_lds[(N::bf_off(l) - N::bf_off(0)) + i * 4 + g];
     unsigned long long m1, m2, m3, m5, m6, m7;
     double lacc = 0.0;
     d4 o8[TF];
-    publish<F, true, 1>(nullptr, img, N::x_off(0), a0, lane, 0);
+    publish<F, true, 1>(nullptr, img, IM::x_off(0), a0, lane, 0);
     {   // ---------------- forward: a layer's tiles live until the next layer has consumed them ----------------
         d4 s7[13];
         {
@@ -321,25 +295,25 @@ __global__ void __launch_bounds__(256) chain64r_kernel(const d4 *packed, const v
                             {
                                 d4 s1[13];
                                 BIAS64R(s1, 0, 13) seq_mm<SQ, 0>(a0, s1, ring, ws, 0); lrelu_rec(s1, m1);
-                                publish<200, true, 1>(nullptr, img, N::x_off(1), s1, lane, 0);
+                                publish<200, true, 1>(nullptr, img, IM::x_off(1), s1, lane, 0);
                                 BIAS64R(s2, 1, 7) seq_mm<SQ, 1>(s1, s2, ring, ws, 0); lrelu_rec(s2, m2);
                             }
-                            publish<100, true, 1>(nullptr, img, N::x_off(2), s2, lane, 0);
+                            publish<100, true, 1>(nullptr, img, IM::x_off(2), s2, lane, 0);
                             BIAS64R(s3, 2, 4) seq_mm<SQ, 2>(s2, s3, ring, ws, 0); lrelu_rec(s3, m3);
                         }
-                        publish<50, true, 1>(nullptr, img, N::x_off(3), s3, lane, 0);
+                        publish<50, true, 1>(nullptr, img, IM::x_off(3), s3, lane, 0);
                         BIAS64R(s4, 3, TZ) seq_mm<SQ, 3>(s3, s4, ring, ws, 0);                                   // en4: no activation
                     }
-                    publish<Z, true, 1>(nullptr, img, N::x_off(4), s4, lane, 0);
+                    publish<Z, true, 1>(nullptr, img, IM::x_off(4), s4, lane, 0);
                     BIAS64R(s5, 4, 4) seq_mm<SQ, 4>(s4, s5, ring, ws, 0); lrelu_rec(s5, m5);
                 }
-                publish<50, true, 1>(nullptr, img, N::x_off(5), s5, lane, 0);
+                publish<50, true, 1>(nullptr, img, IM::x_off(5), s5, lane, 0);
                 BIAS64R(s6, 5, 7) seq_mm<SQ, 5>(s5, s6, ring, ws, 0); lrelu_rec(s6, m6);
             }
-            publish<100, true, 1>(nullptr, img, N::x_off(6), s6, lane, 0);
+            publish<100, true, 1>(nullptr, img, IM::x_off(6), s6, lane, 0);
             BIAS64R(s7, 6, 13) seq_mm<SQ, 6>(s6, s7, ring, ws, 0); lrelu_rec(s7, m7);
         }
-        publish<200, true, 1>(nullptr, img, N::x_off(7), s7, lane, 0);
+        publish<200, true, 1>(nullptr, img, IM::x_off(7), s7, lane, 0);
         BIAS64R(o8, 7, TF) seq_mm<SQ, 7>(s7, o8, ring, ws, 0);                                                   // de4: no activation
     }
 #undef BIAS64R
@@ -353,7 +327,7 @@ __global__ void __launch_bounds__(256) chain64r_kernel(const d4 *packed, const v
             if (live) lacc += d * d;
             o8[t][r] = live ? d * (2.0 / (double)fw) : 0.0;
         }
-    publish<F, false, 1>(nullptr, img, N::z_off(7), o8, lane, 0);
+    publish<F, false, 1>(nullptr, img, IM::z_off(7), o8, lane, 0);
     // ---------------- backward chain (input gradients), publishing the dZ images ----------------
 #define ZERO64(a, NTl) _Pragma("unroll") for (int i = 0; i < NTl; ++i) a[i] = (d4){0.0, 0.0, 0.0, 0.0};
     {
@@ -371,25 +345,25 @@ __global__ void __launch_bounds__(256) chain64r_kernel(const d4 *packed, const v
                             {
                                 d4 d7[13];
                                 ZERO64(d7, 13) seq_mm<SQ, 8>(o8, d7, ring, ws, 0); lrelu_bwd_mask(d7, m7);
-                                publish<200, false, 1>(nullptr, img, N::z_off(6), d7, lane, 0);
+                                publish<200, false, 1>(nullptr, img, IM::z_off(6), d7, lane, 0);
                                 ZERO64(d6, 7) seq_mm<SQ, 9>(d7, d6, ring, ws, 0); lrelu_bwd_mask(d6, m6);
                             }
-                            publish<100, false, 1>(nullptr, img, N::z_off(5), d6, lane, 0);
+                            publish<100, false, 1>(nullptr, img, IM::z_off(5), d6, lane, 0);
                             ZERO64(d5, 4) seq_mm<SQ, 10>(d6, d5, ring, ws, 0); lrelu_bwd_mask(d5, m5);
                         }
-                        publish<50, false, 1>(nullptr, img, N::z_off(4), d5, lane, 0);
+                        publish<50, false, 1>(nullptr, img, IM::z_off(4), d5, lane, 0);
                         ZERO64(d4_, TZ) seq_mm<SQ, 11>(d5, d4_, ring, ws, 0);                                     // dL/dz: en4 has no activation
                     }
-                    publish<Z, false, 1>(nullptr, img, N::z_off(3), d4_, lane, 0);
+                    publish<Z, false, 1>(nullptr, img, IM::z_off(3), d4_, lane, 0);
                     ZERO64(d3, 4) seq_mm<SQ, 12>(d4_, d3, ring, ws, 0); lrelu_bwd_mask(d3, m3);
                 }
-                publish<50, false, 1>(nullptr, img, N::z_off(2), d3, lane, 0);
+                publish<50, false, 1>(nullptr, img, IM::z_off(2), d3, lane, 0);
                 ZERO64(d2, 7) seq_mm<SQ, 13>(d3, d2, ring, ws, 0); lrelu_bwd_mask(d2, m2);
             }
-            publish<100, false, 1>(nullptr, img, N::z_off(1), d2, lane, 0);
+            publish<100, false, 1>(nullptr, img, IM::z_off(1), d2, lane, 0);
             ZERO64(d1, 13) seq_mm<SQ, 14>(d2, d1, ring, ws, 0); lrelu_bwd_mask(d1, m1);
         }
-        publish<200, false, 1>(nullptr, img, N::z_off(0), d1, lane, 0);
+        publish<200, false, 1>(nullptr, img, IM::z_off(0), d1, lane, 0);
     }
 #undef ZERO64
     // loss partial of this 16-row block: the wave's lanes in a fixed order
@@ -398,26 +372,22 @@ __global__ void __launch_bounds__(256) chain64r_kernel(const d4 *packed, const v
     if (lane == 0) loss_part[blk] = lacc;
 }
 
-struct Adam64 {
-    double *params, *pcopy, *m, *v, *packed;
-    const int *sc_off, *sc_idx;
-    double *loss_accum;
-    AdamScalars s;
-};
+using Adam64 = AdamTargets<double>;
 
 // one workgroup per weight-gradient tile: contracts dZ^T (tile nt of layer l) with [X | 1] (tile kt) over all 16-row blocks
 // in a fixed order (wave w takes blocks w, w + 4, ..; then waves 0..3); optionally applies Adam to the parameters it owns.
-enum { DW_WRITE = 0, DW_ADAM = 1 };
+// The tile map, the loss tile, the tile decode, the four-wave sum and the Adam finish are small_step.hpp's; this kernel's own: the range
+// partials (nsplit) and the point at which it requests the scatter slots.
 template <class N, int MODE>
 __global__ void __launch_bounds__(256) dw64_kernel(const double *__restrict__ imgs, int nblk, const double *__restrict__ loss_part,
                                                    const int *__restrict__ inv_map, double *__restrict__ grads, Adam64 ad,
                                                    const double *__restrict__ part, int nsplit, int np, double inv_c, int nloss) {
     // nsplit == 0: the whole job.  nsplit > 0: the tiles' partial sums over `nsplit` block ranges are in `part` (dw64m_kernel); this
     // launch adds them in range order and finishes (store / Adam).
+    using IM = StepImages<N>;
     constexpr int T = N::slab_off(N::L);       // (np, inv_c: the handle's real parameter count and 1 / columns -- class instantiations)
-    constexpr int kPerXcd = (T + 1 + 7) / 8;
     __shared__ __attribute__((aligned(32))) d4 red[4 * 64];
-    const int tile = (blockIdx.x & 7) * kPerXcd + (blockIdx.x >> 3);       // XCD c takes a contiguous tile range (see fused.hip)
+    const int tile = dw_tile_of_block<N>();
     if (tile > T) return;
 #ifdef BAMD_Q4_TRACE
 #define DW_T(i) do { if (tile == 150 && threadIdx.x == 0) g_dw64_trace[(i) - 20] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -425,37 +395,22 @@ __global__ void __launch_bounds__(256) dw64_kernel(const double *__restrict__ im
 #define DW_T(i) do {} while (0)
 #endif
     DW_T(20);
-    if (tile == T) {   // loss: fixed-order sum of the per-block partials, / C
-        const double s = block_sum_fixed(loss_part, nloss, (double *)red);      // (one partial per block, four with the 4-row chain)
-        if (threadIdx.x == 0) {
-            const double gl = s * inv_c;
-            if (grads) grads[np] = gl;
-            if (MODE == DW_ADAM && ad.loss_accum) *ad.loss_accum += gl;
-        }
+    if (tile == T) {   // (one loss partial per block, four with the 4-row chain)
+        dw_loss_tile<MODE>(loss_part, nloss, inv_c, grads, np, ad.loss_accum, (double *)red);
         return;
     }
     const int p = inv_map[tile * 256 + threadIdx.x];
-    int l = 0;
-#pragma unroll
-    for (int j = 1; j < N::L; ++j) if (tile >= N::slab_off(j)) l = j;
-    int nt_count = tiles(N::dim(1)), soff = 0, xo = N::x_off(0), zo = N::z_off(0);
-#pragma unroll
-    for (int j = 1; j < N::L; ++j)
-        if (l == j) { nt_count = tiles(N::dim(j + 1)); soff = N::slab_off(j); xo = N::x_off(j); zo = N::z_off(j); }
-    const int idx = tile - soff, kt = idx / nt_count, nt = idx - kt * nt_count;
+    const DwTile dt = dw_tile_decode<N>(tile);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, i = lane & 15;
     // A[i][k = g] of step r = dZ[slot 16 nt + i][batch row 4 g + r]: four consecutive rows of one image row per lane
-    const double *pz = imgs + ((zo + 16 * nt + i) * 16 + 4 * g);
-    const double *px = imgs + ((xo + 16 * kt + i) * 16 + 4 * g);
+    const double *pz = imgs + ((dt.zo + 16 * dt.nt + i) * IM::stride + 4 * g);
+    const double *px = imgs + ((dt.xo + 16 * dt.kt + i) * IM::stride + 4 * g);
     double pm = 0.0, pv = 0.0, pp = 0.0;
     int s0 = 0, s1 = 0;
     if (MODE == DW_ADAM && p >= 0) { pm = ad.m[p]; pv = ad.v[p]; pp = ad.params[p]; s0 = ad.sc_off[p]; s1 = ad.sc_off[p + 1]; }
     // the packed slots of the parameter (forward and transposed fragment of either chain: up to four) are looked up now, not behind the reduction
-    int sc0 = -1, sc1 = -1, sc2 = -1, sc3 = -1;
-    if (MODE == DW_ADAM && s1 > s0) sc0 = ad.sc_idx[s0];
-    if (MODE == DW_ADAM && s1 > s0 + 1) sc1 = ad.sc_idx[s0 + 1];
-    if (MODE == DW_ADAM && s1 > s0 + 2) sc2 = ad.sc_idx[s0 + 2];
-    if (MODE == DW_ADAM && s1 > s0 + 3) sc3 = ad.sc_idx[s0 + 3];
+    int sc[4] = {-1, -1, -1, -1};
+    if (MODE == DW_ADAM) dw_adam_slots(ad, s0, s1, sc);
     DW_T(21);
     d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
     // (requesting the first UB blocks' image slices BEFORE the parameter index and the optimiser state behind it was measured in round 6:
@@ -469,8 +424,8 @@ __global__ void __launch_bounds__(256) dw64_kernel(const double *__restrict__ im
         for (int u = 0; u < UB; ++u) {
             const int b = b0 + 4 * u;
             const bool ok = b < nblk;
-            a[u] = ok ? *(const d4 *)(pz + (int64_t)b * N::img_doubles) : (d4){0.0, 0.0, 0.0, 0.0};
-            x[u] = ok ? *(const d4 *)(px + (int64_t)b * N::img_doubles) : (d4){0.0, 0.0, 0.0, 0.0};
+            a[u] = ok ? *(const d4 *)(pz + (int64_t)b * IM::size) : (d4){0.0, 0.0, 0.0, 0.0};
+            x[u] = ok ? *(const d4 *)(px + (int64_t)b * IM::size) : (d4){0.0, 0.0, 0.0, 0.0};
         }
 #pragma unroll
         for (int u = 0; u < UB; ++u)
@@ -484,7 +439,7 @@ __global__ void __launch_bounds__(256) dw64_kernel(const double *__restrict__ im
     // thread e = 4 lane' + r' owns D[n slot = g' + 4 r'][k slot = lane' & 15]  (f64 C/D map)
     const double *rf = (const double *)red;
     const int e = threadIdx.x;
-    double gsum = ((rf[e] + rf[256 + e]) + rf[512 + e]) + rf[768 + e];
+    double gsum = dw_sum4(rf, e);
     if (nsplit > 0) {
         gsum = 0.0;
         const double *q = part + (int64_t)tile * nsplit * 256 + e;
@@ -500,18 +455,7 @@ __global__ void __launch_bounds__(256) dw64_kernel(const double *__restrict__ im
     }
     if (p < 0) return;
     if (grads) grads[p] = gsum;
-    if (MODE == DW_ADAM) {   // on the parameters this tile owns
-        const double pn = adam_update(ad.s, gsum, pm, pv, pp);
-        ad.m[p] = pm;
-        ad.v[p] = pv;
-        ad.params[p] = pn;
-        if (ad.pcopy) ad.pcopy[p] = pn;
-        if (sc0 >= 0) ad.packed[sc0] = pn;
-        if (sc1 >= 0) ad.packed[sc1] = pn;
-        if (sc2 >= 0) ad.packed[sc2] = pn;
-        if (sc3 >= 0) ad.packed[sc3] = pn;
-        for (int k = s0 + 4; k < s1; ++k) ad.packed[ad.sc_idx[k]] = pn;
-    }
+    if (MODE == DW_ADAM) dw_adam_finish(ad, p, gsum, pm, pv, pp, sc, s0, s1);   // on the parameters this tile owns
     DW_T(24);
 }
 #undef DW_T
@@ -561,8 +505,9 @@ template <class N> struct Dwx64 {
 template <class N, int l, int MN, int MK, bool CLAMP>
 __device__ __forceinline__ void dw64_tile_block(const double *__restrict__ imgs, int nblk, double *__restrict__ part, int nsplit_total, int accumulate,
                                                 int n0, int k0, d4 *red, int range, int nsplit) {
+    using IM = StepImages<N>;
     constexpr int NA = MN * MK, U = NA >= 12 ? 1 : 2, H0 = (NA + 1) / 2;
-    constexpr int ntc = tiles(N::dim(l + 1)), ktc = tiles(N::dim(l) + 1), soff = N::slab_off(l), xo = N::x_off(l), zo = N::z_off(l);
+    constexpr int ntc = tiles(N::dim(l + 1)), ktc = tiles(N::dim(l) + 1), soff = N::slab_off(l), xo = IM::x_off(l), zo = IM::z_off(l);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, i = lane & 15;
     const double *pz[MN], *px[MK];
     int nt[MN], kt[MK];
@@ -570,13 +515,13 @@ __device__ __forceinline__ void dw64_tile_block(const double *__restrict__ imgs,
     for (int a = 0; a < MN; ++a) {
         nt[a] = n0 + a;
         const int c = !CLAMP || nt[a] < ntc ? nt[a] : ntc - 1;
-        pz[a] = imgs + ((zo + 16 * c + i) * 16 + 4 * g);
+        pz[a] = imgs + ((zo + 16 * c + i) * IM::stride + 4 * g);
     }
 #pragma unroll
     for (int b = 0; b < MK; ++b) {
         kt[b] = k0 + b;
         const int c = !CLAMP || kt[b] < ktc ? kt[b] : ktc - 1;
-        px[b] = imgs + ((xo + 16 * c + i) * 16 + 4 * g);
+        px[b] = imgs + ((xo + 16 * c + i) * IM::stride + 4 * g);
     }
     d4 acc[NA];
 #pragma unroll
@@ -592,7 +537,7 @@ __device__ __forceinline__ void dw64_tile_block(const double *__restrict__ imgs,
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             const int bb = b + 4 * k;
-            const int64_t o = (int64_t)(bb < bhi ? bb : blo) * N::img_doubles;
+            const int64_t o = (int64_t)(bb < bhi ? bb : blo) * IM::size;
 #pragma unroll
             for (int a = 0; a < MN; ++a) za[k][a] = *(const d4 *)(pz[a] + o);
 #pragma unroll
@@ -602,7 +547,7 @@ __device__ __forceinline__ void dw64_tile_block(const double *__restrict__ imgs,
 #pragma unroll
             for (int p = 0; p <= D; ++p) {
                 const int bb = b + 4 * (p + D);
-                const int64_t o = (int64_t)(bb < bhi ? bb : blo) * N::img_doubles;
+                const int64_t o = (int64_t)(bb < bhi ? bb : blo) * IM::size;
 #pragma unroll
                 for (int a = 0; a < MN; ++a) za[(p + D) % (D + 1)][a] = *(const d4 *)(pz[a] + o);
 #pragma unroll
@@ -624,7 +569,7 @@ __device__ __forceinline__ void dw64_tile_block(const double *__restrict__ imgs,
         for (int u = 0; u < U; ++u) {
             const int b = b0 + 4 * u;
             const bool ok = b < bhi;
-            const int64_t o = (int64_t)(ok ? b : blo) * N::img_doubles;
+            const int64_t o = (int64_t)(ok ? b : blo) * IM::size;
 #pragma unroll
             for (int a = 0; a < MN; ++a) { za[u][a] = *(const d4 *)(pz[a] + o); if (!ok) za[u][a] = (d4){0.0, 0.0, 0.0, 0.0}; }
 #pragma unroll
@@ -655,7 +600,7 @@ __device__ __forceinline__ void dw64_tile_block(const double *__restrict__ imgs,
             const int ta = h * H0 + t, c = ta / MN, a = ta % MN;
             if (CLAMP && (nt[a] >= ntc || kt[c] >= ktc)) continue;
             const double *q = rf + t * 1024;
-            const double gsum = ((q[e] + q[256 + e]) + q[512 + e]) + q[768 + e];
+            const double gsum = dw_sum4(q, e);
             const int tile = soff + kt[c] * ntc + nt[a];
             double *dst = part + ((int64_t)tile * nsplit_total + range) * 256 + e;
             *dst = accumulate ? *dst + gsum : gsum;      // chunks after the first add to the range's running sum (chunk order: one stream)
@@ -755,16 +700,17 @@ State64 *st64(bamd_handle *h) { return (State64 *)h->fused64_state; }
 // launch (the tiles themselves for a small batch; loss, range sums, store or Adam).  fw = the table's real width.
 template <class N, class ChainFn>
 int step64_common(bamd_handle *h, State64 *st, int64_t n, double *grads, const Adam64 *ad, hipStream_t s, int fw, ChainFn chain) {
+    using IM = StepImages<N>;
     const int64_t nblk_all = (n + 15) / 16;
     if (nblk_all > (int64_t)1 << 30) { set_error("fp64 fused step: batch too large"); return BAMD_ERR_INVALID; }
     const int64_t chunk = st->chunk_rows & ~(int64_t)15;
     const int nchunk = (int)((n + chunk - 1) / chunk);
     const int nblk_max = (int)((std::min(n, chunk) + 15) / 16);
-    int rc = st->imgs.ensure((size_t)N::img_doubles * sizeof(double) * (size_t)nblk_max);
+    int rc = st->imgs.ensure((size_t)IM::size * sizeof(double) * (size_t)nblk_max);
     if (rc) return rc;
     rc = h->lossp.ensure(sizeof(double) * (size_t)(4 * nblk_all > 1024 ? 4 * nblk_all : 1024));      // (four partials per block with the 4-row chain)
     if (rc) return rc;
-    const dim3 grid(8 * ((N::slab_off(N::L) + 1 + 7) / 8));
+    const dim3 grid(dw_tile_grid<N>());
     // from 64 blocks (1,024 rows) on: 2 x 4 tile blocks over block ranges + the finishing launch (BALER_AMD_DW64_MACRO_BLKS, 0 = off).
     // Measured ms per bamd_fwd_bwd, blocks / one tile per workgroup: 512 rows 0.045 / 0.040, 1,024: 0.046 / 0.049, 2,048: 0.054 / 0.064,
     // 4,096: 0.068 / 0.094, 16,384: 0.227 / 0.341, 65,536: 0.85 / 1.32, 262,144: 3.22 / 5.51 (0.37 / 0.22 of the fp64 MFMA peak)
@@ -826,6 +772,10 @@ int step64_common(bamd_handle *h, State64 *st, int64_t n, double *grads, const A
 // weight-gradient tile owns which parameter, and the CSR scatter lists the Adam kernels refresh the packed copies through.  Geometry
 // (tiles, fragment order, slot -> feature) from the instantiated Net64; which slots hold a parameter, and its canonical index, from
 // the handle's REAL dimensions (identical for an exact instantiation).
+struct Slots64 {      // natural feature order: A-operand row i of tile t = feature 16 t + i; register r on lane group g = creg_feature
+    static int row(int d, int t, int i) { return 16 * t + i < d ? 16 * t + i : -1; }
+    static int reg(int d, int t, int g, int r) { return creg_feature(d, t, g, r); }
+};
 template <class N>
 int build_maps64(bamd_handle *h, State64 *st) {
     const int nparams = (int)h->nparams;
@@ -852,32 +802,8 @@ int build_maps64(bamd_handle *h, State64 *st) {
         for (int l = 0; l < N::L; ++l)
             for (int f = 0; f < dimr(l + 1); ++f) src[q0 + (size_t)N::q_frags() * 128 + N::qb_off(l) + f] = boff(l) + f;
     }
-    for (int l = 0; l < N::L; ++l) {
-        const int K = N::dim(l), NN = N::dim(l + 1), KT = tiles(K), NT = tiles(NN), Kr = dimr(l), NNr = dimr(l + 1);
-        // forward fragment (q, t): lane (i, g) component r = W[16 t + i][16 q + 4 r + g]
-        for (int q = 0; q < KT; ++q)
-            for (int t = 0; t < NT; ++t)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int n = 16 * t + (lane & 15), k = creg_feature(K, q, lane >> 4, r);
-                        if (n < NNr && k >= 0 && k < Kr) src[((size_t)N::wf_off(l) + (q * NT + t) * 64 + lane) * 4 + r] = woff(l) + n * Kr + k;
-                    }
-        // backward fragment (tq, tk), l >= 1: lane (i, g) component r = W[16 tq + 4 r + g][16 tk + i]
-        for (int tq = 0; tq < NT && l >= 1; ++tq)
-            for (int tk = 0; tk < KT; ++tk)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int n = creg_feature(NN, tq, lane >> 4, r), k = 16 * tk + (lane & 15);
-                        if (n >= 0 && n < NNr && k < Kr) src[((size_t)N::wb_off(l) + (tq * KT + tk) * 64 + lane) * 4 + r] = woff(l) + n * Kr + k;
-                    }
-        // bias fragment (t, g) component r = b[16 t + 4 r + g]
-        for (int t = 0; t < NT; ++t)
-            for (int g = 0; g < 4; ++g)
-                for (int r = 0; r < 4; ++r) {
-                    const int n = creg_feature(NN, t, g, r);
-                    if (n >= 0 && n < NNr) src[((size_t)N::bf_off(l) + t * 4 + g) * 4 + r] = boff(l) + n;
-                }
-    }
+    // the 16x16x4 fragments: forward (q, t) W[16 t + i][16 q + 4 r + g], transposed (tq, tk) W[16 tq + 4 r + g][16 tk + i], bias (t, g) b[16 t + 4 r + g]
+    fill_fragment_maps<N>(src, h, Slots64{});
     // weight-gradient tile (kt, nt) of layer l: thread e = 4 lane + r holds dW[16 nt + g + 4 r][16 kt + (lane & 15)]; column K = db
     const int ntiles = N::slab_off(N::L);
     std::vector<int> inv((size_t)ntiles * 256, -1);
@@ -899,12 +825,8 @@ int build_maps64(bamd_handle *h, State64 *st) {
         for (int v : inv) if (v >= 0) seen[v]++;
         for (char c : seen) if (c != 1) { set_error("fp64 fused step: incomplete gradient map"); return BAMD_ERR_INVALID; }
     }
-    std::vector<int> off((size_t)nparams + 1, 0), idx;
-    for (int v : src) if (v >= 0) off[v + 1]++;
-    for (int p = 0; p < nparams; ++p) off[p + 1] += off[p];
-    idx.resize(off[nparams]);
-    std::vector<int> cur(off.begin(), off.end() - 1);
-    for (size_t i = 0; i < src.size(); ++i) if (src[i] >= 0) idx[cur[src[i]]++] = (int)i;
+    std::vector<int> off, idx;
+    invert_pack_map(src, nparams, off, idx);
     st->packed_doubles = (int)src.size();
     int rc = st->pack_src.ensure(src.size() * sizeof(int));
     if (!rc) rc = st->inv_map.ensure(inv.size() * sizeof(int));
@@ -1201,12 +1123,7 @@ int fused64_step(bamd_handle *h, const void *x, int x_dtype, int64_t n, const do
     State64 *st = st64(h);
     if (!st || st->wide || n > st->max_rows || n <= 0) return BAMD_ERR_UNSUPPORTED;
     if (!hp) return st->ops->step(h, st, x, x_dtype, n, features, (double *)grads, nullptr, s);
-    Adam64 ad;
-    ad.params = (double *)params; ad.pcopy = (double *)h->params.p; ad.m = (double *)m; ad.v = (double *)v;
-    ad.packed = (double *)st->packed.p;
-    ad.sc_off = (const int *)st->sc_off.p; ad.sc_idx = (const int *)st->sc_idx.p;
-    ad.loss_accum = loss_accum;
-    ad.s = adam_scalars(*hp);
+    const Adam64 ad = adam_targets<double>(h, params, m, v, st->packed.p, st->sc_off.p, st->sc_idx.p, loss_accum, *hp);
     return st->ops->step(h, st, x, x_dtype, n, features, (double *)grads, &ad, s);
 }
 

@@ -111,6 +111,7 @@ __global__ void __launch_bounds__(256) chain64q_kernel(const double *__restrict_
                                                        const void *__restrict__ xin, int in_f64, int64_t n, const double *__restrict__ feats,
                                                        double *__restrict__ imgs, double *__restrict__ loss_part, int fr) {
     using N = Net64<F, Z>;
+    using IM = StepImages<N>;
     using T = Q4<N>;
     static_assert(F % 16 != 0 && F <= 127, "input rows: up to two 64-slot halves x 4 rows per thread");
     __shared__ __attribute__((aligned(16))) double lds[T::lds_doubles];
@@ -123,7 +124,7 @@ __global__ void __launch_bounds__(256) chain64q_kernel(const double *__restrict_
     if (nwg % 32 == 0) { blk = (wg >> 5) * 8 + (wg & 7); quad = (wg >> 3) & 3; }
     Q4_T(0);
     const int fw = RT ? fr : F;                                    // the table's real width (row stride, valid features, loss scale)
-    double *img = imgs + (int64_t)blk * N::img_doubles + 4 * quad;
+    double *img = imgs + (int64_t)blk * IM::size + 4 * quad;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)qpacked, 0, N::q_frags() * 1024, 0x00020000);
     const int lane16 = lane * 16;
     // ---- request order = order of use: the 4 input rows (HBM), the biases, then the fragment ring
@@ -160,7 +161,7 @@ __global__ void __launch_bounds__(256) chain64q_kernel(const double *__restrict_
         v = f < fw ? v : 0.0;
         if (f == F) v = 1.0;                                         // the ones slot (carries db) sits at the class width
         if (f < 16 * tiles(F)) lds[T::xo(0) + tj * T::xs(0) + f] = v;
-        if (f < N::x_rows(0)) img[(N::x_off(0) + f) * 16 + tj] = v;
+        if (f < IM::x_rows(0)) img[(IM::x_off(0) + f) * IM::stride + tj] = v;
     }
 #pragma unroll
     for (int i = 0; i < kNBI; ++i) {
@@ -208,7 +209,7 @@ __global__ void __launch_bounds__(256) chain64q_kernel(const double *__restrict_
             if (N::act(l)) v = v > 0.0 ? v : v * kSlope;                                                                     \
             if (f == N::dim((l) + 1)) v = 1.0;                                                                               \
             lds[T::xo((l) + 1) + j * T::xs((l) + 1) + f] = v;                                                                \
-            img[(N::x_off((l) + 1) + f) * 16 + j] = v;                                                                       \
+            img[(IM::x_off((l) + 1) + f) * IM::stride + j] = v;                                                                       \
         };                                                                                                                   \
         Q_GEMM(l, T::xo(l), T::xs(l), fin)                                                                                   \
         Q4_T(3 + (l));                                                                                                       \
@@ -223,7 +224,7 @@ __global__ void __launch_bounds__(256) chain64q_kernel(const double *__restrict_
             if (live) lacc += d * d;
             const double dz = live ? d * (2.0 / (double)fw) : 0.0;
             lds[T::zo(1) + j * T::zs + f] = dz;
-            img[(N::z_off(7) + f) * 16 + j] = dz;
+            img[(IM::z_off(7) + f) * IM::stride + j] = dz;
         };
         Q_GEMM(7, T::xo(7), T::xs(7), fin)
         Q4_T(10);
@@ -234,7 +235,7 @@ __global__ void __launch_bounds__(256) chain64q_kernel(const double *__restrict_
         auto fin = [&](double v, int f, int j, bool) {                                                                       \
             if (N::act((l) - 1)) v = lds[T::xo(l) + j * T::xs(l) + f] > 0.0 ? v : v * kSlope;                                \
             lds[T::zo(((l) - 1) & 1) + j * T::zs + f] = v;                                                                   \
-            img[(N::z_off((l) - 1) + f) * 16 + j] = v;                                                                       \
+            img[(IM::z_off((l) - 1) + f) * IM::stride + j] = v;                                                                       \
         };                                                                                                                   \
         Q_GEMM(15 - (l), T::zo((l) & 1), T::zs, fin)                                                                         \
         Q4_T(18 - (l));                                                                                                      \

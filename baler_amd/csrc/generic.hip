@@ -1222,10 +1222,7 @@ template <typename T> struct SmallDwPlan {
 };
 // `ad.on`: the optimiser step of exactly these parameters in the same launch, the refresh of their packed copies included
 template <typename T> struct SmallAdamT {
-    T *p, *pcopy, *m, *v, *packed;
-    const int *sc_off, *sc_idx;
-    double *loss_accum;
-    AdamScalars s;
+    AdamTargets<T> t;
     int64_t np;
     int on;
 };
@@ -1242,7 +1239,7 @@ __global__ void __launch_bounds__(256) dw_small_all_k(SmallDwPlan<T> pl, int64_t
         if (threadIdx.x == 0) {
             const T lv = accumulate ? (T)((double)grads[np] + s) : (T)s;
             grads[np] = lv;
-            if (ad.on && ad.loss_accum) *ad.loss_accum += (double)lv;
+            if (ad.on && ad.t.loss_accum) *ad.t.loss_accum += (double)lv;
         }
         return;
     }
@@ -1293,8 +1290,8 @@ __global__ void __launch_bounds__(256) dw_small_all_k(SmallDwPlan<T> pl, int64_t
         const int64_t q = pidx[r] < 0 ? 0 : pidx[r];
         gv[r] = accumulate ? grads[q] + acc[r] : acc[r];
         if (ad.on) {
-            pm[r] = ad.m[q]; pv[r] = ad.v[q]; pp[r] = ad.p[q];
-            so0[r] = ad.packed ? ad.sc_off[q] : 0; so1[r] = ad.packed ? ad.sc_off[q + 1] : 0;
+            pm[r] = ad.t.m[q]; pv[r] = ad.t.v[q]; pp[r] = ad.t.params[q];
+            so0[r] = ad.t.packed ? ad.t.sc_off[q] : 0; so1[r] = ad.t.packed ? ad.t.sc_off[q + 1] : 0;
         }
     }
 #pragma unroll
@@ -1302,12 +1299,12 @@ __global__ void __launch_bounds__(256) dw_small_all_k(SmallDwPlan<T> pl, int64_t
         if (pidx[r] < 0) continue;
         grads[pidx[r]] = gv[r];
         if (ad.on) {
-            const T pn = adam_update(ad.s, gv[r], pm[r], pv[r], pp[r]);
-            ad.m[pidx[r]] = pm[r];
-            ad.v[pidx[r]] = pv[r];
-            ad.p[pidx[r]] = pn;
-            if (ad.pcopy) ad.pcopy[pidx[r]] = pn;
-            for (int k = so0[r]; k < so1[r]; ++k) ad.packed[ad.sc_idx[k]] = pn;
+            const T pn = adam_update(ad.t.s, gv[r], pm[r], pv[r], pp[r]);
+            ad.t.m[pidx[r]] = pm[r];
+            ad.t.v[pidx[r]] = pv[r];
+            ad.t.params[pidx[r]] = pn;
+            if (ad.t.pcopy) ad.t.pcopy[pidx[r]] = pn;
+            for (int k = so0[r]; k < so1[r]; ++k) ad.t.packed[ad.t.sc_idx[k]] = pn;
         }
     }
 }
@@ -1493,13 +1490,11 @@ int generic_small_train_step(bamd_handle *h, const void *x, int x_dtype, int64_t
                              void *m, void *v, const bamd_adam &hp, double *loss_accum, hipStream_t s) {
     if (h->esize != 4) return BAMD_ERR_UNSUPPORTED;
     if (env_off("BALER_AMD_SMALL_ADAM")) return BAMD_ERR_UNSUPPORTED;
-    SmallAdam sa{};
-    sa.p = (float *)params; sa.pcopy = (float *)h->params.p; sa.m = (float *)m; sa.v = (float *)v;
+    const int *sc_off = nullptr, *sc_idx = nullptr;
     void *packed = nullptr;
-    fused_scatter(h, &sa.sc_off, &sa.sc_idx, &packed);
-    sa.packed = (float *)packed;
-    sa.loss_accum = loss_accum;
-    sa.s = adam_scalars(hp);
+    fused_scatter(h, &sc_off, &sc_idx, &packed);
+    SmallAdam sa{};
+    sa.t = adam_targets<float>(h, params, m, v, packed, sc_off, sc_idx, loss_accum, hp);
     sa.np = h->nparams;
     sa.on = 1;
     return fwd_bwd_T<float>(h, x, x_dtype, n, features, grads, nullptr, s, &sa);
