@@ -163,6 +163,20 @@ __global__ void convert_latent_k(const void *__restrict__ x, int sd, void *__res
         latent_store<float>(out, dd, i, latent_load<float>(x, sd, i));
 }
 
+// 8-bit latent codes (BAMD_U8, latent_io.hpp: code8_store / code8_load) either side of the float32 latent workspace.  One element per
+// lane: consecutive lanes read consecutive floats and write consecutive bytes (64 contiguous bytes per wave store), whatever the
+// row start and width -- byte rows of 15, 7 or 9 codes are never 4-byte aligned, so nothing is packed.
+__global__ void code8_store_k(const float *__restrict__ x, uint8_t *__restrict__ out, int64_t count) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
+         i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = code8_store(x[i]);
+}
+__global__ void code8_load_k(const uint8_t *__restrict__ x, float *__restrict__ out, int64_t count) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
+         i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = code8_load(x[i]);
+}
+
 static inline int ew_grid(int64_t count) {
     int64_t b = (count + 255) / 256;
     return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
@@ -203,7 +217,11 @@ int launch_renormalize(const void *x, int dtype, int64_t n, int c, const double 
 int launch_convert(const void *src, int sd, void *dst, int dd, int64_t count, hipStream_t s) {
     if (count == 0) return BAMD_OK;
     dim3 g(ew_grid(count)), b(256);
-    if (dtype_half(sd) || dtype_half(dd))
+    if (dtype_code8(sd) || dtype_code8(dd)) {      // only against the float32 latent workspace (bamd_encode / bamd_decode)
+        BAMD_REQUIRE((dtype_code8(dd) && sd == BAMD_F32) || (dtype_code8(sd) && dd == BAMD_F32), "8-bit codes convert from and to float32 only");
+        if (dtype_code8(dd)) hipLaunchKernelGGL(code8_store_k, g, b, 0, s, (const float *)src, (uint8_t *)dst, count);
+        else hipLaunchKernelGGL(code8_load_k, g, b, 0, s, (const uint8_t *)src, (float *)dst, count);
+    } else if (dtype_half(sd) || dtype_half(dd))
         hipLaunchKernelGGL(convert_latent_k, g, b, 0, s, src, sd, dst, dd, count);
     else if (sd == BAMD_F64 && dd == BAMD_F64)
         hipLaunchKernelGGL((convert_k<double, double>), g, b, 0, s, (const double *)src, (double *)dst, count);

@@ -18,7 +18,8 @@ namespace bamd {
 
 inline bool dtype_wide(int d) { return d == BAMD_F32 || d == BAMD_F64; }        // legal for every dtype argument
 inline bool dtype_half(int d) { return d == BAMD_F16 || d == BAMD_BF16; }       // legal as the latent of bamd_encode / bamd_decode only
-inline size_t dtype_bytes(int d) { return d == BAMD_F64 ? 8 : d == BAMD_F32 ? 4 : 2; }
+inline bool dtype_code8(int d) { return d == BAMD_U8; }                         // 8-bit codes (bamd_code8): the same two places, always through the float32 workspace
+inline size_t dtype_bytes(int d) { return d == BAMD_F64 ? 8 : d == BAMD_F32 ? 4 : d == BAMD_U8 ? 1 : 2; }
 
 #if defined(__HIPCC__)
 // float32 -> binary16 bits: v_cvt_f16_f32, round to nearest even (the truncating pack conversion is NOT used anywhere)
@@ -49,6 +50,17 @@ template <typename S> __device__ __forceinline__ S latent_load(const void *base,
     if (dtype == BAMD_F32) return (S)((const float *)base)[i];
     return (S)half_widen(dtype, ((const uint16_t *)base)[i]);
 }
+// 8-bit codes (include/baler_amd.h, bamd_code8): the ONE definition of their store and load.  Deliberately NOT a case of
+// latent_store / latent_load / half_bits above: those inline into the encode / decode kernels, whose register budgets stay as
+// they are; only the row-conversion kernels of elementwise.hip use these two.
+// float32 latent -> code: rintf (half to even), clamped to [0, 255]; NaN fails both comparisons' "keep" side and gives 0.
+__device__ __forceinline__ uint8_t code8_store(float v) {
+    float r = rintf(v);
+    r = r > 0.0f ? r : 0.0f;          // NaN, -inf, negatives, -0 -> 0
+    r = r < 255.0f ? r : 255.0f;      // +inf -> 255
+    return (uint8_t)r;
+}
+__device__ __forceinline__ float code8_load(uint8_t q) { return (float)q; }      // exact
 #endif
 
 }  // namespace bamd

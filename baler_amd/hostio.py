@@ -36,20 +36,22 @@ NP_OF_TORCH = {torch.float32: np.float32, torch.float64: np.float64, torch.float
                torch.uint8: np.uint8, torch.int32: np.int32, torch.int64: np.int64}
 
 
-# ---- 16-bit latent codes in compressed.npz --------------------------------------------------------------------------------
+# ---- 16-bit and 8-bit latent codes in compressed.npz -------------------------------------------------------------------------
 # config.latent_dtype -> the torch dtype of the latent buffer.  float16 codes are stored as a numpy float16 `data`; numpy has no
 # bfloat16, so those are stored as their uint16 bit patterns plus the key latent_dtype = "bfloat16".  Archives without the key are
 # recognised by data.dtype (float16 / float32 / float64), so everything written before the key existed loads as it always did.
-LATENT_DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16}
+# 8-bit codes ("uint8"): a uint8 `data`, the key latent_dtype = "uint8" and latent_scale, float64 (2, z) = [min ; range] of the
+# latent columns -- the affine map that baler_amd.latent8 folds into the model on either side.
+LATENT_DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16, "uint8": torch.uint8}
 
 
 def parse_latent_dtype(value):
-    """config.latent_dtype -> None (codes at the working precision, the default) | "float16" | "bfloat16"; else ValueError."""
+    """config.latent_dtype -> None (codes at the working precision, the default) | "float16" | "bfloat16" | "uint8"; else ValueError."""
     if value is None:
         return None
     if isinstance(value, str) and value in LATENT_DTYPES:
         return value
-    raise ValueError(f"latent_dtype must be None, \"float16\" or \"bfloat16\", got {value!r}")
+    raise ValueError(f"latent_dtype must be None, \"float16\", \"bfloat16\" or \"uint8\", got {value!r}")
 
 
 def bf16_bits(a):
@@ -65,33 +67,72 @@ def bf16_widen(bits):
     return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
-def latent_to_archive(codes, latent_dtype=None):
+def check_latent_scale(scale, z_dim):
+    """latent_scale of 8-bit codes: float64 (2, z_dim) = [min ; range], every entry finite, no negative range; else ValueError."""
+    a = np.asarray(scale)
+    if a.dtype.kind != "f" or a.shape != (2, int(z_dim)):
+        raise ValueError(f"latent_scale must be a float64 array of shape (2, {int(z_dim)}) = [min ; range], got {a.dtype} {a.shape}")
+    a = a.astype(np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError("latent_scale has a non-finite entry")
+    if (a[1] < 0).any():
+        raise ValueError("latent_scale has a negative range")
+    return a
+
+
+def latent_to_archive(codes, latent_dtype=None, scale=None):
     """The latent member(s) of compressed.npz as np.savez keywords.  codes: float32 / float64 (latent_dtype None), numpy float16
-    ("float16"), or the uint16 bit patterns of bfloat16 codes ("bfloat16")."""
+    ("float16"), the uint16 bit patterns of bfloat16 codes ("bfloat16"), or uint8 codes with their ``scale`` ("uint8": float64
+    (2, z) = [min ; range] of the latent columns)."""
     latent_dtype = parse_latent_dtype(latent_dtype)
+    if latent_dtype != "uint8" and scale is not None:
+        raise ValueError("a latent scale belongs to latent_dtype = \"uint8\" only")
     if latent_dtype is None:
         return {"data": codes}
     if latent_dtype == "float16":
         if codes.dtype != np.float16:
             raise ValueError(f"float16 latent codes expected, got {codes.dtype}")
         return {"data": codes}
+    if latent_dtype == "uint8":
+        if codes.dtype != np.uint8 or codes.ndim != 2:
+            raise ValueError(f"uint8 latent codes of shape (N, z) expected, got {codes.dtype} {codes.shape}")
+        if scale is None:
+            raise ValueError("latent_dtype = \"uint8\" needs the latent scale")
+        return {"data": codes, "latent_dtype": np.array("uint8"), "latent_scale": check_latent_scale(scale, codes.shape[1])}
     if codes.dtype != np.uint16:
         raise ValueError(f"bfloat16 latent codes travel as uint16 bit patterns, got {codes.dtype}")
     return {"data": codes, "latent_dtype": np.array("bfloat16")}
 
 
 def latent_from_archive(data, archive_keys, read_key):
-    """-> (host array to upload, torch dtype of 16-bit codes or None).  ``data``: the archive's `data` member (memory-mapped or
-    loaded), ``archive_keys``: the archive's member names, ``read_key(name)``: loads one.  bfloat16 bit patterns come back viewed
-    as float16 -- a 2-byte carrier that every copy moves verbatim; the device tensor is re-viewed as bfloat16."""
+    """-> (host array to upload, torch dtype of 16-bit / 8-bit codes or None).  ``data``: the archive's `data` member (memory-mapped
+    or loaded), ``archive_keys``: the archive's member names, ``read_key(name)``: loads one.  bfloat16 bit patterns come back viewed
+    as float16 -- a 2-byte carrier that every copy moves verbatim; the device tensor is re-viewed as bfloat16.  uint8 codes come
+    back as they are; their archive is checked here (latent_scale_from_archive) and the scale is read with that function."""
     if "latent_dtype" in archive_keys:
         name = str(read_key("latent_dtype"))
+        if name == "uint8":
+            latent_scale_from_archive(data, archive_keys, read_key)
+            return data, torch.uint8
         if name != "bfloat16" or data.dtype != np.uint16:
             raise ValueError(f"compressed archive: latent_dtype = {name!r} with data of {data.dtype} is not a format this version writes")
         return data.view(np.float16), torch.bfloat16
     if data.dtype == np.float16:
         return data, torch.float16
     return data, None
+
+
+def latent_scale_from_archive(data, archive_keys, read_key):
+    """The float64 (2, z) latent_scale of an archive of 8-bit codes (None for every other archive).  ValueError for what this
+    version does not write: latent_dtype = "uint8" with a `data` that is not a uint8 (N, z) array, without latent_scale, or with a
+    latent_scale of the wrong shape, with a non-finite entry or with a negative range."""
+    if "latent_dtype" not in archive_keys or str(read_key("latent_dtype")) != "uint8":
+        return None
+    if data.dtype != np.uint8 or data.ndim != 2:
+        raise ValueError(f"compressed archive: latent_dtype = 'uint8' with data of {data.dtype} {tuple(data.shape)} is not a format this version writes")
+    if "latent_scale" not in archive_keys:
+        raise ValueError("compressed archive: latent_dtype = 'uint8' without latent_scale")
+    return check_latent_scale(read_key("latent_scale"), data.shape[1])
 
 
 def _pool():
@@ -287,9 +328,11 @@ def _staging(slot, rows, tail, dtype):
 def _device_dtype(np_dtype, keep_half=False):
     """float32 / float64 tables keep their dtype; anything else is converted to float64 on the host chunk
     (the reference does the same implicitly when it builds float64 tensors, training.py:230).  keep_half: float16 stays float16
-    (16-bit latent codes; tables never take this route)."""
+    and uint8 stays uint8 (16-bit / 8-bit latent codes, moved verbatim; tables never take this route)."""
     if keep_half and np_dtype == np.float16:
         return torch.float16, np.float16
+    if keep_half and np_dtype == np.uint8:
+        return torch.uint8, np.uint8
     if np_dtype == np.float32:
         return torch.float32, np.float32
     return torch.float64, np.float64

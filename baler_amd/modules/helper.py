@@ -19,6 +19,7 @@ sys.path.append(os.getcwd())
 
 from .. import dist as bdist
 from .. import hostio
+from .. import latent8
 from .. import native
 from . import data_processing, training
 
@@ -360,6 +361,33 @@ def _check_float16_range(h, flat, feats, out, world):
                          "(float32's range at 8 bits of precision) or leave latent_dtype unset.")
 
 
+def _calibrate_latent8(h, flat, feats, world):
+    """config.latent_dtype = "uint8", first pass: the extrema of every latent column over ALL rows -> (2, z) float64 numpy
+    [min ; range].  Per ROW_BLOCK one float32 encode and one bamd_col_minmax; the blocks' 2 x z doubles are combined on the device,
+    the ranks' with one MIN and one MAX all-reduce (exact in any order, so every rank count gives the same scale).  A non-finite
+    extremum (a NaN or inf latent: bamd_col_minmax propagates NaN) raises ValueError on every rank, before anything is written."""
+    z = h.z_dim
+    mm = torch.stack([torch.full((z,), float("inf"), dtype=torch.float64, device=flat.device),
+                      torch.full((z,), float("-inf"), dtype=torch.float64, device=flat.device)])      # a rank without rows: neutral
+    for s in range(0, flat.shape[0], ROW_BLOCK):
+        e = min(s + ROW_BLOCK, flat.shape[0])
+        blk = native.col_minmax(h.encode(flat[s:e], features=feats, out_dtype=torch.float32))
+        nan = torch.isnan(blk).any(dim=0) | torch.isnan(mm).any(dim=0)
+        mm = torch.stack([torch.minimum(mm[0], blk[0]), torch.maximum(mm[1], blk[1])])
+        mm[:, nan] = float("nan")
+    if world > 1:
+        bdist.allreduce_minmax(mm)
+    mm = mm.cpu().numpy()
+    with np.errstate(all="ignore"):
+        scale = np.stack([mm[0], mm[1] - mm[0]])
+    if not (np.isfinite(mm).all() and np.isfinite(scale).all()):
+        bad = int((~(np.isfinite(mm) & np.isfinite(scale)).all(axis=0)).sum())
+        raise ValueError(f"latent_dtype = \"uint8\": {bad} of {z} latent columns have a non-finite minimum or maximum over this table "
+                         "(a NaN or inf row, or a model that overflows on it), so there is no scale for the codes; no archive is "
+                         "written.  Use latent_dtype = \"float16\" / \"bfloat16\" or leave latent_dtype unset.")
+    return scale
+
+
 def _check_fp16_mode_range(h, rows_in, rows_out, world, what):
     """The fp16 and fp16x3 compute modes (BAMD_MODE_F16 / BAMD_MODE_F16X3: binary16 layer inputs, include/baler_amd.h): a value beyond
     +-65504 inside the chain turns every output of ITS row non-finite.  Count, on the device, the rows whose input is entirely finite
@@ -394,7 +422,12 @@ def compress(model_path, config):
     ``config.latent_dtype`` = "float16" / "bfloat16": the latent buffer has that dtype -- bamd_encode rounds the codes on the device, so
     the gather, the download and the archive move 2 bytes per code; float16 codes come back as a numpy float16 array, bfloat16 codes
     as their uint16 bit patterns (hostio.latent_to_archive).  The deltas side channel is computed from decode() of the ROUNDED codes,
-    which is what decompress will decode."""
+    which is what decompress will decode.
+
+    ``config.latent_dtype`` = "uint8": two passes.  The first finds the extrema of every latent column (_calibrate_latent8); the map
+    of [min, min + range] onto [0, 255] is then folded into the last encoder and the first decoder layer of THIS RUN's copy of the
+    parameters (baler_amd.latent8; model.pt is not touched), and the second pass encodes to bytes: 1 byte per code.  The scale is
+    left in ``config.latent_scale`` for the archive; the deltas come from decode() of the bytes on the folded handle."""
     want_deltas = bool(getattr(config, "save_error_bounded_deltas", False))
     latent_dtype = latent_dtype_of(config)          # (a bad value fails here, before any GPU work)
     rank, world = bdist.rank_world()
@@ -423,6 +456,12 @@ def compress(model_path, config):
     model.eval()
     h = model.handle()
     n_local = flat.shape[0]
+    if latent_dtype == "uint8":
+        # the affine map of the codes goes INTO the model of this run (model.pt stays as it is): from here on h emits the latent in
+        # code units [0, 255], and decodes them.  config.latent_scale: what perform_compression writes next to the codes.
+        config.latent_scale = _calibrate_latent8(h, flat, feats, world)
+        model.load_flat(latent8.fold(model, config.latent_scale[0], config.latent_scale[1]))
+        h = model.handle()
     out = torch.empty((n_local, config.latent_space_size), dtype=hostio.LATENT_DTYPES.get(latent_dtype, work_dtype), device=flat.device)
     if want_deltas:
         flags = torch.empty((n_local, n_features), dtype=torch.uint8, device=flat.device)
@@ -442,7 +481,15 @@ def compress(model_path, config):
         ready.append((e, ev))
     if latent_dtype == "float16":       # before the gather and the download: an overflowing run fails without moving the codes
         _check_float16_range(h, flat, feats, out, world)
-    _check_fp16_mode_range(h, flat, out, world, "encode")
+    checked = out
+    if latent_dtype == "uint8" and h.compute_mode in (native.MODE_F16, native.MODE_F16X3):
+        # a byte cannot show a non-finite latent (NaN is stored as 0): the fp16 modes' range check reads the folded handle's float32
+        # latent instead -- a tiny range makes a large folded weight, which can leave the float16 range where the plain model did not
+        checked = torch.empty(out.shape, dtype=torch.float32, device=out.device)
+        for s in range(0, n_local, ROW_BLOCK):
+            e = min(s + ROW_BLOCK, n_local)
+            h.encode(flat[s:e], features=feats, out=checked[s:e])
+    _check_fp16_mode_range(h, flat, checked, world, "encode")
     # bfloat16 codes travel as a float16-typed view: a 2-byte carrier every collective and numpy know; no copy interprets it
     compressed = _gather_rows(out.view(torch.float16) if latent_dtype == "bfloat16" else out, n_total, world, ready)
     if latent_dtype == "bfloat16":
@@ -544,6 +591,7 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
     normalization_features = loaded["normalization_features"]
     # 16-bit codes are recognised from the ARCHIVE (data.dtype / its latent_dtype key), never from the config
     data, code_dtype = hostio.latent_from_archive(data, loaded.files, lambda k: loaded[k])
+    latent_scale = hostio.latent_scale_from_archive(data, loaded.files, lambda k: loaded[k])      # 8-bit codes only (else None)
     latent_space_size = data.shape[1]
     model_dict = torch.load(str(model_path), map_location="cpu")
     number_of_columns = len(model_dict[list(model_dict.keys())[-1]])  # len(de4.bias), helper.py:668-674
@@ -556,6 +604,8 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
         model = data_processing.load_model(data_processing.initialise_model(config.model_name), model_path,
                                            n_features=number_of_columns, z_dim=latent_space_size)
     model.eval()
+    if latent_scale is not None:      # 8-bit codes: this run's copy of the parameters decodes code units (model.pt is not touched)
+        model.load_flat(latent8.fold(model, latent_scale[0], latent_scale[1]))
     h = model.handle()
     rank, world = bdist.rank_world()
     n_total = data.shape[0]

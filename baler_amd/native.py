@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("BALER_AMD_LIB", os.path.join(_HERE, "libbaler_amd.so"
 
 F32, F64 = 0, 1
 F16, BF16 = 2, 3        # 16-bit latent codes: the z of bamd_encode / bamd_decode only (include/baler_amd.h, bamd_dtype)
-MODE_F32, MODE_F64, MODE_BF16, MODE_F16 = 0, 1, 2, 3      # MODE_F16: binary16 inference of the 24-column AE, fp32 training
+U8 = 8                  # 8-bit latent codes (bamd_code8): the same two places; rint + clamp to [0, 255] on store, exact widening on load
+MODE_F32, MODE_F64, MODE_BF16, MODE_F16 = 0, 1, 2, 3     # MODE_F16: binary16 inference of the 24-column AE, fp32 training
 MODE_F16X3 = 5      # fp32 accuracy from three binary16 MFMA products per tile (24-column AE inference, fp32 training); 4 is not a mode
 MODE_NAMES = {"fp32": MODE_F32, "f32": MODE_F32, "fp64": MODE_F64, "f64": MODE_F64, "bf16": MODE_BF16, "fp16": MODE_F16, "f16": MODE_F16,
               "fp16x3": MODE_F16X3, "f16x3": MODE_F16X3}
@@ -125,11 +126,13 @@ def _dt(t):
 
 
 def _dt_latent(t):
-    """dtype code of a latent tensor: float32 / float64 as everywhere, or the 16-bit code types of bamd_encode / bamd_decode."""
+    """dtype code of a latent tensor: float32 / float64 as everywhere, or the 16-bit / 8-bit code types of bamd_encode / bamd_decode."""
     if t.dtype == torch.float16:
         return F16
     if t.dtype == torch.bfloat16:
         return BF16
+    if t.dtype == torch.uint8:
+        return U8
     return _dt(t)
 
 
@@ -464,7 +467,9 @@ class Handle:
     def encode(self, x, features=None, out_dtype=None, out=None):
         """z = encode(x).  out_dtype (or the dtype of ``out``): float32 / float64, or torch.float16 / torch.bfloat16 for 16-bit
         codes -- the round-to-nearest-even conversion of the float32 codes, made on the device by bamd_encode (inside the encode kernel
-        for the fp32 register chain, bf16.hip and the layer-wise path; one conversion launch behind a float32 workspace otherwise)."""
+        for the fp32 register chain, bf16.hip and the layer-wise path; one conversion launch behind a float32 workspace otherwise).
+        torch.uint8: 8-bit codes, q = clamp(rint(float32 code), 0, 255) -- workspace and conversion launch for every family; the
+        parameters are expected to carry the latent scale (baler_amd.latent8.fold)."""
         x = _dev_tensor(x)
         self._mine(x, features)
         out = self._out(out, x.shape[0], self.z_dim, out_dtype or x.dtype, x.device)
@@ -473,7 +478,7 @@ class Handle:
         return out
 
     def decode(self, z, features=None, int_mask=None, out_dtype=None, out=None):
-        """out = decode(z).  z may hold float16 / bfloat16 codes: they are widened exactly, the result is that of the widened
+        """out = decode(z).  z may hold float16 / bfloat16 / uint8 codes: they are widened exactly, the result is that of the widened
         float32 codes bit for bit (default output dtype then: float32)."""
         z = _dev_tensor(z)
         self._mine(z, features, int_mask)

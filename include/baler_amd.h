@@ -66,6 +66,20 @@ typedef enum bamd_status {
  * Widening a code on bamd_decode is exact: the result equals bamd_decode of the widened float32 codes bit for bit. */
 typedef enum bamd_dtype { BAMD_F32 = 0, BAMD_F64 = 1, BAMD_F16 = 2, BAMD_BF16 = 3 } bamd_dtype;
 
+/* 8-bit latent codes: a CODE KIND, not an element type -- no table can have it, so it is not a member of the enum above.
+ * BAMD_U8 is legal in exactly two places: z_dtype of bamd_encode (the output) and z_dtype of bamd_decode (the input); the buffer
+ * is (n_rows, z_dim) bytes, row-major, unpadded.  Every other dtype argument of every entry point returns BAMD_ERR_INVALID for
+ * it, with a message that names the argument, before anything is launched or written.
+ * Store: let v be the value the same handle would have stored as BAMD_F32 (a BAMD_MODE_F64 handle rounds its float64 latent to
+ * float32 first).  The code is q = (uint8) min(max(rint(v), 0), 255), rint being round-half-to-even in float32 (rintf).  NaN
+ * gives 0, -inf gives 0, +inf gives 255.
+ * Load: float32(q) is exact; a decode of BAMD_U8 codes equals the decode of their float32 widening bit for bit, the fused
+ * un-normalise and int-truncation epilogue included.
+ * The library knows nothing about a scale: a caller that wants a latent in [0, 255] folds its per-column affine map into the
+ * last encoder layer and the first decoder layer of the parameters it loads (baler_amd/latent8.py does).  For every family the
+ * codes pass through the handle's float32 latent workspace and one row-conversion launch; no encode or decode kernel changes. */
+typedef enum bamd_code8 { BAMD_U8 = 8 } bamd_code8;
+
 /* arithmetic the Linear layers run in.  F32 = v_mfma_f32_16x16x4_f32 (exact fp32, the parity mode:
  * outputs within 1e-5 rel. of the fp64 reference).  F64 = v_mfma_f64_16x16x4_f64 (long-horizon
  * training parity).  BF16 = v_mfma_f32_16x16x32_bf16 with fp32 accumulation: a THROUGHPUT mode with its own 2e-2 bar.
@@ -302,13 +316,14 @@ int bamd_renormalize(const void *x, int dtype, int64_t n_rows, int n_cols, const
  * z: (n_rows, z_dim) row-major, z_dtype: BAMD_F32 / BAMD_F64, or BAMD_F16 / BAMD_BF16 for 16-bit codes (2 bytes per element,
  * rounded as described at bamd_dtype; the conversion is part of the encode launch for the fp32 register-chain, bf16 and
  * layer-wise kernels, and one row-conversion launch behind a float32 workspace for the wide-layer kernels, the fp64 chain,
- * FPGA_prototype_model and PJ_Conv_AE).  x_dtype is BAMD_F32 or BAMD_F64. */
+ * FPGA_prototype_model and PJ_Conv_AE), or BAMD_U8 for 8-bit codes (1 byte per element, see bamd_code8: float32 workspace and
+ * one row-conversion launch for every family).  x_dtype is BAMD_F32 or BAMD_F64. */
 int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features,
                 void *z, int z_dtype, void *stream);
 /* Replaces: AE.decode (models.py:147-152) as driven by helper.decompress (helper.py:700-723), with
  * the optional un-normalise + int-column truncation epilogue of baler.py:420-435 fused in when
  * features != NULL (int_mask may still be NULL).  z_dtype may be BAMD_F16 / BAMD_BF16: the codes are widened exactly on load and
- * the result is bit-identical to decoding the widened float32 codes.  out_dtype is BAMD_F32 or BAMD_F64. */
+ * the result is bit-identical to decoding the widened float32 codes; BAMD_U8 codes likewise.  out_dtype is BAMD_F32 or BAMD_F64. */
 int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, const double *features,
                 const uint8_t *int_mask, void *out, int out_dtype, void *stream);
 /* Replaces: AE.forward (models.py:154-156) + utils.mse_sum_loss_l1(validate=True)
