@@ -139,9 +139,9 @@ def perform_compression(output_path, config, verbose: bool):
     names = np.load(config.input_path)["names"]
     saver = np.savez_compressed if config.extra_compression else np.savez
     # config.latent_dtype: float16 codes are a float16 `data`; bfloat16 codes are uint16 bit patterns + the key latent_dtype
-    # uint8 codes: a uint8 `data`, the key, and latent_scale = [min ; range] of the latent columns (helper.compress left it in the config)
+    # uint8 codes and packed "uint1" .. "uint7" rows: a uint8 `data`, the key, and latent_scale = [min ; range] of the latent columns (helper.compress left it in the config)
     latent_dtype = helper.latent_dtype_of(config)
-    fields = hostio.latent_to_archive(compressed, latent_dtype, scale=config.latent_scale if latent_dtype == "uint8" else None)
+    fields = hostio.latent_to_archive(compressed, latent_dtype, scale=config.latent_scale if hostio.latent_bits(latent_dtype) is not None else None)
     saver(os.path.join(output_path, "compressed_output", "compressed.npz"), data=fields.pop("data"), names=names,
           normalization_features=normalization_features, **fields)
     if getattr(config, "save_error_bounded_deltas", False):    # baler.py:316-338

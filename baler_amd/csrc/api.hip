@@ -119,7 +119,7 @@ int open_device(const char *fn, int device, DeviceGuard &guard) {
     }
     return BAMD_OK;
 }
-// bamd_encode / bamd_decode with 8-bit codes, or with 16-bit codes on a family that does not convert them in its kernels (latent_in_kernel below), chunk by
+// bamd_encode / bamd_decode with 8-bit or packed sub-byte codes, or with 16-bit codes on a family that does not convert them in its kernels (latent_in_kernel below), chunk by
 // chunk: body(r0, rows) finds room for `rows` float32 latent rows in h->lat32 (at most 256 MiB of them; BALER_AMD_LAT32_ROWS: several
 // chunks at small sizes, for tests) and converts on its side of the family call.
 template <typename Body>
@@ -137,10 +137,10 @@ int lat32_chunks(bamd_handle *h, int64_t n_rows, Body body) {
 }
 }  // namespace
 
-// BAMD_F16 / BAMD_BF16 / BAMD_U8 are storage types of latent codes: legal as z_dtype of bamd_encode / bamd_decode and nowhere else.
+// BAMD_F16 / BAMD_BF16 / BAMD_U8 / BAMD_U1 .. BAMD_U7 are storage types of latent codes: legal as z_dtype of bamd_encode / bamd_decode and nowhere else.
 // Every other dtype argument is checked here, by name, before anything is launched or written.
 #define BAMD_WIDE_DTYPE(d, name) \
-    BAMD_REQUIRE(dtype_wide(d), name " must be BAMD_F32 or BAMD_F64 (BAMD_F16 / BAMD_BF16 / BAMD_U8 are latent codes: z_dtype of bamd_encode / bamd_decode only)")
+    BAMD_REQUIRE(dtype_wide(d), name " must be BAMD_F32 or BAMD_F64 (BAMD_F16 / BAMD_BF16 / BAMD_U8 / BAMD_U1 .. BAMD_U7 are latent codes: z_dtype of bamd_encode / bamd_decode only)")
 
 extern "C" {
 
@@ -415,8 +415,9 @@ static int infer_rows(bamd_handle *h, InferKind kind, const void *in, int in_dty
 // the launch that touches the latent anyway (latent_io.hpp).  The wide-layer kernels, the fp64 chain, the FPGA_prototype_model
 // kernels and the PJ_Conv_AE kernels keep their float32 / float64 stores: their latent goes through a float32 workspace and ONE row-conversion
 // launch -- the same rounding (float32 first, then 16 bits) and the same exact widening, so the results are bit-identical either way.
-// 8-bit codes (BAMD_U8) take the workspace route on EVERY family: no encode / decode kernel knows them (latent_io.hpp), so the
-// callers below ask this only for 16-bit codes.
+// 8-bit codes (BAMD_U8) and packed sub-byte codes (BAMD_U1 .. BAMD_U7) take the workspace route on EVERY family: no encode / decode
+// kernel knows them (latent_io.hpp), so the callers below ask this only for 16-bit codes.  Packed rows are byte-aligned
+// (latent_row_bytes), so the workspace chunk that starts at row r0 starts at byte r0 * zrow like every other kind.
 static bool latent_in_kernel(const bamd_handle *h) {
     const Family f = infer_family(h);      // (Fused: the register chain; the wide-layer kernels: workspace)
     return f == Family::Bf16 || f == Family::F16 || f == Family::F16X3 || f == Family::Generic || (f == Family::Fused && fused_latent_in_kernel(h));
@@ -425,25 +426,27 @@ int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, cons
                 int z_dtype, void *stream) {
     BAMD_CHECK_MODEL(h);
     BAMD_WIDE_DTYPE(x_dtype, "x_dtype");
-    BAMD_REQUIRE(dtype_wide(z_dtype) || dtype_half(z_dtype) || dtype_code8(z_dtype), "z_dtype must be BAMD_F32, BAMD_F64, BAMD_F16, BAMD_BF16 or BAMD_U8");
+    BAMD_REQUIRE(dtype_wide(z_dtype) || dtype_half(z_dtype) || dtype_code8(z_dtype) || dtype_codeb(z_dtype),
+                 "z_dtype must be BAMD_F32, BAMD_F64, BAMD_F16, BAMD_BF16, BAMD_U8 or BAMD_U1 .. BAMD_U7");
     BAMD_REQUIRE(n_rows >= 0 && ((x && z) || n_rows == 0), "bad arguments");
     if (n_rows == 0) return BAMD_OK;
     hipStream_t s = (hipStream_t)stream;
     if (dtype_wide(z_dtype) || (dtype_half(z_dtype) && latent_in_kernel(h)))
         return infer_rows(h, K_ENCODE, x, x_dtype, n_rows, features, z, z_dtype, nullptr, nullptr, nullptr, s);
     const int64_t zd = h->dims[h->L / 2];
-    const size_t xrow = (size_t)h->dims[0] * dtype_bytes(x_dtype), zrow = (size_t)zd * dtype_bytes(z_dtype);
+    const size_t xrow = (size_t)h->dims[0] * dtype_bytes(x_dtype), zrow = latent_row_bytes(zd, z_dtype);
     return lat32_chunks(h, n_rows, [&](int64_t r0, int64_t rows) {
         const int rc = infer_rows(h, K_ENCODE, (const char *)x + (size_t)r0 * xrow, x_dtype, rows, features, h->lat32.p, BAMD_F32, nullptr,
                                   nullptr, nullptr, s);
-        return rc ? rc : launch_convert(h->lat32.p, BAMD_F32, (char *)z + (size_t)r0 * zrow, z_dtype, rows * zd, s);
+        return rc ? rc : launch_convert_rows(h->lat32.p, BAMD_F32, (char *)z + (size_t)r0 * zrow, z_dtype, rows, (int)zd, s);
     });
 }
 
 int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, const double *features,
                 const uint8_t *int_mask, void *out, int out_dtype, void *stream) {
     BAMD_CHECK_MODEL(h);
-    BAMD_REQUIRE(dtype_wide(z_dtype) || dtype_half(z_dtype) || dtype_code8(z_dtype), "z_dtype must be BAMD_F32, BAMD_F64, BAMD_F16, BAMD_BF16 or BAMD_U8");
+    BAMD_REQUIRE(dtype_wide(z_dtype) || dtype_half(z_dtype) || dtype_code8(z_dtype) || dtype_codeb(z_dtype),
+                 "z_dtype must be BAMD_F32, BAMD_F64, BAMD_F16, BAMD_BF16, BAMD_U8 or BAMD_U1 .. BAMD_U7");
     BAMD_WIDE_DTYPE(out_dtype, "out_dtype");
     BAMD_REQUIRE(n_rows >= 0 && ((z && out) || n_rows == 0), "bad arguments");
     if (n_rows == 0) return BAMD_OK;
@@ -451,9 +454,9 @@ int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, cons
     if (dtype_wide(z_dtype) || (dtype_half(z_dtype) && latent_in_kernel(h)))
         return infer_rows(h, K_DECODE, z, z_dtype, n_rows, nullptr, out, out_dtype, features, int_mask, nullptr, s);
     const int64_t zd = h->dims[h->L / 2];
-    const size_t zrow = (size_t)zd * dtype_bytes(z_dtype), orow = (size_t)h->dims[h->L] * dtype_bytes(out_dtype);
+    const size_t zrow = latent_row_bytes(zd, z_dtype), orow = (size_t)h->dims[h->L] * dtype_bytes(out_dtype);
     return lat32_chunks(h, n_rows, [&](int64_t r0, int64_t rows) {
-        const int rc = launch_convert((const char *)z + (size_t)r0 * zrow, z_dtype, h->lat32.p, BAMD_F32, rows * zd, s);
+        const int rc = launch_convert_rows((const char *)z + (size_t)r0 * zrow, z_dtype, h->lat32.p, BAMD_F32, rows, (int)zd, s);
         return rc ? rc : infer_rows(h, K_DECODE, h->lat32.p, BAMD_F32, rows, nullptr, (char *)out + (size_t)r0 * orow, out_dtype, features,
                                     int_mask, nullptr, s);
     });

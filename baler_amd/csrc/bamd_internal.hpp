@@ -120,6 +120,8 @@ int launch_renormalize(const void *x, int dtype, int64_t n, int c, const double 
                        const uint8_t *int_mask, double *out, hipStream_t s);
 int launch_convert(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t count,
                    hipStream_t s);
+int launch_convert_rows(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t rows, int z,
+                        hipStream_t s);   // latent rows against the float32 workspace: packed codes (bamd_codeb) need the row shape
 int launch_emd_rows(const void *x, const void *recon, int dtype, int64_t n, int c, double *out,
                     hipStream_t s);
 int launch_emd_rows_wide(const void *x, const void *recon, int dtype, int64_t n, int c, double *out,

@@ -177,6 +177,91 @@ __global__ void code8_load_k(const uint8_t *__restrict__ x, float *__restrict__ 
         out[i] = code8_load(x[i]);
 }
 
+// Packed b-bit latent codes (bamd_codeb, latent_io.hpp: codeb_store / codeb_load) either side of the float32 latent workspace.  A
+// workgroup takes `rpb` whole rows at a time (decided on the host, so that everything inside is a small int): their packed
+// bytes are one contiguous range, and inside it there is only 32-bit arithmetic without a division instruction.  b, z and S are
+// kernel ARGUMENTS: there is one store and one load kernel.  Inside, b is a uniform switch into bodies that know it as a constant
+// (constant shifts, a fixed number of loads that are all in flight together); the per-lane split of an index into (row,
+// position) multiplies by a reciprocal the host made.  All of this came from measurements: the packed
+// route reads what the uint8 route reads and writes less, so what it costs over that route is its own instructions.
+// t / d by the host's m = ceil(2^32 / d), exact for t * d < 2^32; m = 0 stands for d = 1 and m = 1 for "always 0" (rpb = 1)
+__device__ __forceinline__ int div_magic(int t, uint32_t m) { return m ? (int)__umulhi((uint32_t)t, m) : t; }
+
+// Store: one lane per GROUP of 8 codes, which is exactly B bytes: group g of a row is its codes 8g .. 8g + 7 and its bytes
+// g B .. g B + B - 1, so no code straddles two lanes and every float is quantised once.  The lane packs its codes into one
+// 64-bit word (code 8g + i at bit i B, at most 56 bits) and stores the word's B low bytes one by one -- byte stores, because a
+// row of S bytes starts at any byte address.  The last group of a row may be short: a code past the row contributes nothing
+// (its load is clamped to the row's last float, so no float outside the rows is read), which also makes the padding bits of the
+// row's last byte zero, and a byte past the row's S bytes is not stored, so no byte outside the rows is touched.
+// (One lane per output byte, the first shape of this kernel, quantised a straddling code twice and spent about 60 instructions
+// per byte on index arithmetic and 64-bit addresses: profiles/latentb_bench_lane_per_byte.json.)
+template <int B>
+__device__ __forceinline__ void codeb_store_rows(const float *__restrict__ x, uint8_t *__restrict__ out, int64_t rows, int z, int S, int rpb,
+                                                 uint32_t mG) {
+    const int G = (z + 7) >> 3;      // groups per row
+    for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < rows; r0 += (int64_t)gridDim.x * rpb) {
+        const int nr = (int)(rows - r0 < rpb ? rows - r0 : rpb);
+        const float *__restrict__ xb = x + r0 * z;
+        uint8_t *__restrict__ ob = out + r0 * S;
+        for (int t = threadIdx.x; t < nr * G; t += blockDim.x) {
+            const int r = div_magic(t, mG), g = t - r * G;
+            const float *__restrict__ xr = xb + r * z;
+            const int k0 = 8 * g, left = z - k0;      // left >= 1 codes of the row from k0 on
+            uint64_t word = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float v = xr[k0 + (i < left ? i : left - 1)];
+                word |= (uint64_t)(i < left ? codeb_store(v, B) : 0u) << (i * B);
+            }
+            uint8_t *__restrict__ og = ob + r * S + g * B;
+            const int nb = S - g * B;                   // >= 1 bytes of the row from g B on
+#pragma unroll
+            for (int i = 0; i < B; ++i)
+                if (i < nb) og[i] = (uint8_t)(word >> (8 * i));
+        }
+    }
+}
+__global__ void __launch_bounds__(256) codeb_store_k(const float *__restrict__ x, uint8_t *__restrict__ out, int64_t rows, int z, int S,
+                                                     int bits, int rpb, uint32_t mG) {
+    switch (bits) {
+    case 1: codeb_store_rows<1>(x, out, rows, z, S, rpb, mG); break;
+    case 2: codeb_store_rows<2>(x, out, rows, z, S, rpb, mG); break;
+    case 3: codeb_store_rows<3>(x, out, rows, z, S, rpb, mG); break;
+    case 4: codeb_store_rows<4>(x, out, rows, z, S, rpb, mG); break;
+    case 5: codeb_store_rows<5>(x, out, rows, z, S, rpb, mG); break;
+    case 6: codeb_store_rows<6>(x, out, rows, z, S, rpb, mG); break;
+    case 7: codeb_store_rows<7>(x, out, rows, z, S, rpb, mG); break;
+    default: break;      // (launch_convert_rows passes 1 .. 7 only)
+    }
+}
+// Load: one lane per code, consecutive lanes write consecutive floats.
+template <int B>
+__device__ __forceinline__ void codeb_load_rows(const uint8_t *__restrict__ x, float *__restrict__ out, int64_t rows, int z, int S, int rpb,
+                                                uint32_t mz) {
+    for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < rows; r0 += (int64_t)gridDim.x * rpb) {
+        const int nr = (int)(rows - r0 < rpb ? rows - r0 : rpb);
+        const uint8_t *__restrict__ xb = x + r0 * S;
+        float *__restrict__ ob = out + r0 * z;
+        for (int t = threadIdx.x; t < nr * z; t += blockDim.x) {
+            const int r = div_magic(t, mz), k = t - r * z;
+            ob[t] = codeb_load(xb + r * S, k, B);
+        }
+    }
+}
+__global__ void __launch_bounds__(256) codeb_load_k(const uint8_t *__restrict__ x, float *__restrict__ out, int64_t rows, int z, int S,
+                                                    int bits, int rpb, uint32_t mz) {
+    switch (bits) {
+    case 1: codeb_load_rows<1>(x, out, rows, z, S, rpb, mz); break;
+    case 2: codeb_load_rows<2>(x, out, rows, z, S, rpb, mz); break;
+    case 3: codeb_load_rows<3>(x, out, rows, z, S, rpb, mz); break;
+    case 4: codeb_load_rows<4>(x, out, rows, z, S, rpb, mz); break;
+    case 5: codeb_load_rows<5>(x, out, rows, z, S, rpb, mz); break;
+    case 6: codeb_load_rows<6>(x, out, rows, z, S, rpb, mz); break;
+    case 7: codeb_load_rows<7>(x, out, rows, z, S, rpb, mz); break;
+    default: break;
+    }
+}
+
 static inline int ew_grid(int64_t count) {
     int64_t b = (count + 255) / 256;
     return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
@@ -214,7 +299,29 @@ int launch_renormalize(const void *x, int dtype, int64_t n, int c, const double 
     return BAMD_OK;
 }
 
+// `rows` latent rows of `z` codes between the float32 workspace and the caller's codes of any kind.  Packed codes need the row
+// shape; every other kind is a flat conversion of rows * z elements.
+int launch_convert_rows(const void *src, int sd, void *dst, int dd, int64_t rows, int z, hipStream_t s) {
+    if (!dtype_codeb(sd) && !dtype_codeb(dd)) return launch_convert(src, sd, dst, dd, rows * z, s);
+    BAMD_REQUIRE((dtype_codeb(dd) && sd == BAMD_F32) || (dtype_codeb(sd) && dd == BAMD_F32), "packed codes convert from and to float32 only");
+    BAMD_REQUIRE(src && dst && rows >= 0 && z > 0 && z < (1 << 27), "bad arguments");
+    if (rows == 0) return BAMD_OK;
+    const int code = dtype_codeb(dd) ? dd : sd, bits = codeb_bits(code), S = (int)latent_row_bytes(z, code);
+    // the reciprocal of the row split (div_magic): t < rpb * d <= 1024 + d and d <= 1024 wherever rpb > 1, so t * d < 2^32
+    auto magic = [](int d, int rpb) { return rpb == 1 ? 1u : d == 1 ? 0u : (uint32_t)((((uint64_t)1 << 32) + d - 1) / d); };
+    // rows per workgroup visit: about four passes of its 256 lanes -- over a row's groups of 8 codes (store) or its codes (load)
+    const int per_row = dtype_codeb(dd) ? (z + 7) / 8 : z, rpb = per_row < 1024 ? 1024 / per_row : 1;
+    const int64_t groups = (rows + rpb - 1) / rpb;
+    dim3 g((unsigned)(groups < 2048 ? groups : 2048)), b(256);
+    if (dtype_codeb(dd))
+        hipLaunchKernelGGL(codeb_store_k, g, b, 0, s, (const float *)src, (uint8_t *)dst, rows, z, S, bits, rpb, magic(per_row, rpb));
+    else hipLaunchKernelGGL(codeb_load_k, g, b, 0, s, (const uint8_t *)src, (float *)dst, rows, z, S, bits, rpb, magic(per_row, rpb));
+    BAMD_HIP(hipGetLastError());
+    return BAMD_OK;
+}
+
 int launch_convert(const void *src, int sd, void *dst, int dd, int64_t count, hipStream_t s) {
+    BAMD_REQUIRE(!dtype_codeb(sd) && !dtype_codeb(dd), "packed codes convert row by row (launch_convert_rows)");
     if (count == 0) return BAMD_OK;
     dim3 g(ew_grid(count)), b(256);
     if (dtype_code8(sd) || dtype_code8(dd)) {      // only against the float32 latent workspace (bamd_encode / bamd_decode)

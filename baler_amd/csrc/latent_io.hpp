@@ -20,6 +20,13 @@ inline bool dtype_wide(int d) { return d == BAMD_F32 || d == BAMD_F64; }        
 inline bool dtype_half(int d) { return d == BAMD_F16 || d == BAMD_BF16; }       // legal as the latent of bamd_encode / bamd_decode only
 inline bool dtype_code8(int d) { return d == BAMD_U8; }                         // 8-bit codes (bamd_code8): the same two places, always through the float32 workspace
 inline size_t dtype_bytes(int d) { return d == BAMD_F64 ? 8 : d == BAMD_F32 ? 4 : d == BAMD_U8 ? 1 : 2; }
+// packed b-bit codes, b = 1 .. 7 (bamd_codeb, 0x100 | b): the same two places and the same workspace route as 8-bit codes.  An
+// element of a packed row has no size in bytes, so dtype_bytes() has no answer for them; a ROW has one: latent_row_bytes().
+inline bool dtype_codeb(int d) { return d >= BAMD_U1 && d <= BAMD_U7; }
+inline int codeb_bits(int d) { return d & 0xff; }
+inline size_t latent_row_bytes(int64_t z_dim, int d) {      // bytes of one latent row of z_dim codes: rows are byte-aligned
+    return dtype_codeb(d) ? (size_t)((z_dim * codeb_bits(d) + 7) / 8) : (size_t)z_dim * dtype_bytes(d);
+}
 
 #if defined(__HIPCC__)
 // float32 -> binary16 bits: v_cvt_f16_f32, round to nearest even (the truncating pack conversion is NOT used anywhere)
@@ -61,6 +68,23 @@ __device__ __forceinline__ uint8_t code8_store(float v) {
     return (uint8_t)r;
 }
 __device__ __forceinline__ float code8_load(uint8_t q) { return (float)q; }      // exact
+// Packed b-bit codes (include/baler_amd.h, bamd_codeb), b = 1 .. 7: the ONE definition of their store and load, and as above no
+// case of latent_store / latent_load.  The store rule is code8_store's with 2^b - 1 in the place of 255.
+__device__ __forceinline__ uint32_t codeb_store(float v, int bits) {
+    const float top = (float)((1u << bits) - 1u);
+    float r = rintf(v);
+    r = r > 0.0f ? r : 0.0f;          // NaN, -inf, negatives, -0 -> 0
+    r = r < top ? r : top;            // +inf -> 2^b - 1
+    return (uint32_t)r;
+}
+// code k of the packed row `row`: bits [k b, (k + 1) b) of the row's bit string, bit i being bit i % 8 of byte i / 8.  The second
+// byte is read only when the code reaches into it, and then it is a byte of the row: (k + 1) b <= z b <= 8 S.
+__device__ __forceinline__ float codeb_load(const uint8_t *__restrict__ row, int k, int bits) {
+    const int bit = k * bits, j = bit >> 3, sh = bit & 7;
+    uint32_t w = row[j];
+    if (sh + bits > 8) w |= (uint32_t)row[j + 1] << 8;
+    return (float)((w >> sh) & ((1u << bits) - 1u));      // exact; padding bits are never part of a code
+}
 #endif
 
 }  // namespace bamd

@@ -42,16 +42,27 @@ NP_OF_TORCH = {torch.float32: np.float32, torch.float64: np.float64, torch.float
 # recognised by data.dtype (float16 / float32 / float64), so everything written before the key existed loads as it always did.
 # 8-bit codes ("uint8"): a uint8 `data`, the key latent_dtype = "uint8" and latent_scale, float64 (2, z) = [min ; range] of the
 # latent columns -- the affine map that baler_amd.latent8 folds into the model on either side.
-LATENT_DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16, "uint8": torch.uint8}
+# Packed sub-byte codes ("uint1" .. "uint7", b bits each): the same three members, `data` being uint8 (N, ceil(z * b / 8)) -- byte-
+# aligned packed rows (baler_amd.latent8.pack_rows states the layout); z is latent_scale.shape[1], there is no further key.
+LATENT_DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16, "uint8": torch.uint8,
+                 **{f"uint{b}": torch.uint8 for b in range(1, 8)}}
+
+
+def latent_bits(name):
+    """Bits per code of an integer code type: 8 for "uint8", b for "uint<b>", b = 1 .. 7; None for every other latent_dtype."""
+    if isinstance(name, str) and name in LATENT_DTYPES and name.startswith("uint"):
+        return int(name[4:])
+    return None
 
 
 def parse_latent_dtype(value):
-    """config.latent_dtype -> None (codes at the working precision, the default) | "float16" | "bfloat16" | "uint8"; else ValueError."""
+    """config.latent_dtype -> None (codes at the working precision, the default) | "float16" | "bfloat16" | "uint8" | "uint1" ..
+    "uint7"; else ValueError."""
     if value is None:
         return None
     if isinstance(value, str) and value in LATENT_DTYPES:
         return value
-    raise ValueError(f"latent_dtype must be None, \"float16\", \"bfloat16\" or \"uint8\", got {value!r}")
+    raise ValueError(f"latent_dtype must be None, \"float16\", \"bfloat16\", \"uint8\" or \"uint1\" .. \"uint7\", got {value!r}")
 
 
 def bf16_bits(a):
@@ -68,7 +79,7 @@ def bf16_widen(bits):
 
 
 def check_latent_scale(scale, z_dim):
-    """latent_scale of 8-bit codes: float64 (2, z_dim) = [min ; range], every entry finite, no negative range; else ValueError."""
+    """latent_scale of 8-bit and packed codes: float64 (2, z_dim) = [min ; range], every entry finite, no negative range; else ValueError."""
     a = np.asarray(scale)
     if a.dtype.kind != "f" or a.shape != (2, int(z_dim)):
         raise ValueError(f"latent_scale must be a float64 array of shape (2, {int(z_dim)}) = [min ; range], got {a.dtype} {a.shape}")
@@ -80,13 +91,20 @@ def check_latent_scale(scale, z_dim):
     return a
 
 
+def packed_row_bytes(z, bits):
+    """Bytes of one byte-aligned packed row of z codes of ``bits`` bits."""
+    return (int(z) * int(bits) + 7) // 8
+
+
 def latent_to_archive(codes, latent_dtype=None, scale=None):
     """The latent member(s) of compressed.npz as np.savez keywords.  codes: float32 / float64 (latent_dtype None), numpy float16
     ("float16"), the uint16 bit patterns of bfloat16 codes ("bfloat16"), or uint8 codes with their ``scale`` ("uint8": float64
-    (2, z) = [min ; range] of the latent columns)."""
+    (2, z) = [min ; range] of the latent columns), or packed rows of b-bit codes with their scale ("uint1" .. "uint7": uint8
+    (N, ceil(z * b / 8)), z being the scale's width)."""
     latent_dtype = parse_latent_dtype(latent_dtype)
-    if latent_dtype != "uint8" and scale is not None:
-        raise ValueError("a latent scale belongs to latent_dtype = \"uint8\" only")
+    bits = latent_bits(latent_dtype)
+    if bits is None and scale is not None:
+        raise ValueError("a latent scale belongs to latent_dtype = \"uint8\" and \"uint1\" .. \"uint7\" only")
     if latent_dtype is None:
         return {"data": codes}
     if latent_dtype == "float16":
@@ -99,6 +117,14 @@ def latent_to_archive(codes, latent_dtype=None, scale=None):
         if scale is None:
             raise ValueError("latent_dtype = \"uint8\" needs the latent scale")
         return {"data": codes, "latent_dtype": np.array("uint8"), "latent_scale": check_latent_scale(scale, codes.shape[1])}
+    if bits is not None:
+        if scale is None:
+            raise ValueError(f"latent_dtype = \"{latent_dtype}\" needs the latent scale")
+        z = np.asarray(scale).shape[-1] if np.asarray(scale).ndim == 2 else -1
+        scale = check_latent_scale(scale, z)
+        if codes.dtype != np.uint8 or codes.ndim != 2 or codes.shape[1] != packed_row_bytes(z, bits):
+            raise ValueError(f"packed {bits}-bit latent codes of {z} columns are uint8 (N, {packed_row_bytes(z, bits)}), got {codes.dtype} {codes.shape}")
+        return {"data": codes, "latent_dtype": np.array(latent_dtype), "latent_scale": scale}
     if codes.dtype != np.uint16:
         raise ValueError(f"bfloat16 latent codes travel as uint16 bit patterns, got {codes.dtype}")
     return {"data": codes, "latent_dtype": np.array("bfloat16")}
@@ -108,10 +134,10 @@ def latent_from_archive(data, archive_keys, read_key):
     """-> (host array to upload, torch dtype of 16-bit / 8-bit codes or None).  ``data``: the archive's `data` member (memory-mapped
     or loaded), ``archive_keys``: the archive's member names, ``read_key(name)``: loads one.  bfloat16 bit patterns come back viewed
     as float16 -- a 2-byte carrier that every copy moves verbatim; the device tensor is re-viewed as bfloat16.  uint8 codes come
-    back as they are; their archive is checked here (latent_scale_from_archive) and the scale is read with that function."""
+    and packed rows come back as they are; their archive is checked here (latent_scale_from_archive) and the scale is read with that function."""
     if "latent_dtype" in archive_keys:
         name = str(read_key("latent_dtype"))
-        if name == "uint8":
+        if latent_bits(name) is not None:      # "uint8": one byte per code; "uint1" .. "uint7": packed rows, moved verbatim too
             latent_scale_from_archive(data, archive_keys, read_key)
             return data, torch.uint8
         if name != "bfloat16" or data.dtype != np.uint16:
@@ -123,11 +149,24 @@ def latent_from_archive(data, archive_keys, read_key):
 
 
 def latent_scale_from_archive(data, archive_keys, read_key):
-    """The float64 (2, z) latent_scale of an archive of 8-bit codes (None for every other archive).  ValueError for what this
+    """The float64 (2, z) latent_scale of an archive of 8-bit or packed b-bit codes (None for every other archive; for packed
+    codes z, the number of latent columns, is the scale's width).  ValueError for what this
     version does not write: latent_dtype = "uint8" with a `data` that is not a uint8 (N, z) array, without latent_scale, or with a
     latent_scale of the wrong shape, with a non-finite entry or with a negative range."""
-    if "latent_dtype" not in archive_keys or str(read_key("latent_dtype")) != "uint8":
+    name = str(read_key("latent_dtype")) if "latent_dtype" in archive_keys else None
+    bits = latent_bits(name)
+    if bits is None:
         return None
+    if bits < 8:      # packed rows: z is the scale's width, and data must be uint8 (N, ceil(z * bits / 8))
+        if "latent_scale" not in archive_keys:
+            raise ValueError(f"compressed archive: latent_dtype = {name!r} without latent_scale")
+        scale = np.asarray(read_key("latent_scale"))
+        scale = check_latent_scale(scale, scale.shape[1] if scale.ndim == 2 and scale.shape[1] > 0 else -1)
+        z = scale.shape[1]
+        if data.dtype != np.uint8 or data.ndim != 2 or data.shape[1] != packed_row_bytes(z, bits):
+            raise ValueError(f"compressed archive: latent_dtype = {name!r} with a latent_scale of {z} columns needs data of uint8 "
+                             f"(N, {packed_row_bytes(z, bits)}), got {data.dtype} {tuple(data.shape)}")
+        return scale
     if data.dtype != np.uint8 or data.ndim != 2:
         raise ValueError(f"compressed archive: latent_dtype = 'uint8' with data of {data.dtype} {tuple(data.shape)} is not a format this version writes")
     if "latent_scale" not in archive_keys:

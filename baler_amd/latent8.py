@@ -1,4 +1,6 @@
-"""8-bit latent codes, host side: the rounding rule of BAMD_U8 stated in NumPy, and the per-column scale FOLDED INTO THE MODEL.
+"""8-bit and packed sub-byte latent codes, host side: the rounding rule of BAMD_U8 / BAMD_U1 .. BAMD_U7 and the bit layout of packed
+rows stated in NumPy, and the per-column scale FOLDED INTO THE MODEL.  The text below speaks of bytes and 255; b-bit codes are the
+same with ``levels(b)`` = 2**b - 1 in the place of 255 (the ``levels`` arguments) plus pack_rows / unpack_rows.
 
 The library stores a float32 latent as a byte by rounding it to the nearest integer in [0, 255] and widens a byte exactly
 (include/baler_amd.h, bamd_code8); it knows nothing about a scale.  A latent column k with calibrated extrema lo_k, lo_k + rng_k
@@ -32,11 +34,69 @@ def widen8(q):
     return q.astype(np.float32)
 
 
-def scale_of(rng):
-    """s_k = 255 / rng_k where rng_k > 0, else 1 (a constant latent column: every code is 0 and decodes to lo_k)."""
+def levels(bits):
+    """The largest code of ``bits`` bits, 2**bits - 1 (bits = 1 .. 8): the value a column's calibrated maximum is mapped to."""
+    bits = int(bits)
+    if not 1 <= bits <= 8:
+        raise ValueError(f"latent codes have 1 to 8 bits, got {bits}")
+    return 2 ** bits - 1
+
+
+def row_bytes(z, bits):
+    """Bytes of one packed row of z codes of ``bits`` bits: ceil(z * bits / 8) -- rows are byte-aligned."""
+    return (int(z) * int(bits) + 7) // 8
+
+
+def qb(v, bits):
+    """The store rule of b-bit codes (include/baler_amd.h, bamd_codeb): q8 with 2**bits - 1 in the place of 255; qb(v, 8) is q8(v).
+    -> uint8, one code per element, NOT yet packed."""
+    top = np.float32(levels(bits))
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = np.rint(np.asarray(v).astype(np.float32))
+        r = np.where(r > 0, r, np.float32(0))          # NaN fails the comparison: 0
+        r = np.where(r < top, r, top)
+        return r.astype(np.uint8)
+
+
+def pack_rows(q, bits):
+    """Codes (n, z), each below 2**bits -> packed rows, uint8 (n, ceil(z * bits / 8)).  Code k of a row occupies bits
+    [k * bits, (k + 1) * bits) of the row's bit string; bit i of a row is bit i % 8 of its byte i // 8; the unused high bits of the
+    last byte are zero.  Written from that rule: every code is shifted to its place and its (at most two) bytes are OR-ed in."""
+    q = np.asarray(q)
+    bits = int(bits)
+    if q.ndim != 2 or q.dtype != np.uint8 or not 1 <= bits <= 8 or (q.size and int(q.max()) > levels(bits)):
+        raise ValueError(f"pack_rows: uint8 codes of shape (n, z) below 2**{bits} expected")
+    n, z = q.shape
+    out = np.zeros((n, row_bytes(z, bits) + 1), dtype=np.uint8)      # (one spare byte takes the empty high half of the last code)
+    start = np.arange(z) * bits
+    byte, sh = start // 8, start % 8
+    for k in range(z):
+        w = q[:, k].astype(np.uint16) << np.uint16(sh[k])
+        out[:, byte[k]] |= (w & 0xFF).astype(np.uint8)
+        out[:, byte[k] + 1] |= (w >> np.uint16(8)).astype(np.uint8)
+    return np.ascontiguousarray(out[:, :-1])
+
+
+def unpack_rows(data, z, bits):
+    """Packed rows, uint8 (n, ceil(z * bits / 8)) -> codes, uint8 (n, z); the padding bits of the last byte are ignored."""
+    data = np.asarray(data)
+    z, bits = int(z), int(bits)
+    if data.ndim != 2 or data.dtype != np.uint8 or not 1 <= bits <= 8 or data.shape[1] != row_bytes(z, bits):
+        raise ValueError(f"unpack_rows: uint8 rows of {row_bytes(z, bits)} bytes expected for {z} codes of {bits} bits, got {data.dtype} {data.shape}")
+    wide = np.concatenate([data, np.zeros((data.shape[0], 1), dtype=np.uint8)], axis=1).astype(np.uint16)
+    out = np.empty((data.shape[0], z), dtype=np.uint8)
+    for k in range(z):
+        j, sh = (k * bits) // 8, (k * bits) % 8
+        w = wide[:, j] | (wide[:, j + 1] << np.uint16(8))
+        out[:, k] = ((w >> np.uint16(sh)) & np.uint16(levels(bits))).astype(np.uint8)
+    return out
+
+
+def scale_of(rng, levels=255):
+    """s_k = levels / rng_k where rng_k > 0, else 1 (a constant latent column: every code is 0 and decodes to lo_k)."""
     rng = np.asarray(rng, dtype=np.float64)
     s = np.ones_like(rng)
-    np.divide(255.0, rng, out=s, where=rng > 0)
+    np.divide(float(levels), rng, out=s, where=rng > 0)
     return s
 
 
@@ -51,12 +111,12 @@ def latent_tensors(layout):
     return (layout[2 * e], layout[2 * e + 1]), (layout[2 * d], layout[2 * d + 1])
 
 
-def fold_flat(flat, layout, lo, rng):
+def fold_flat(flat, layout, lo, rng, levels=255):
     """The fold on a flat parameter vector (any float array; the result is float64, NOT yet rounded): a copy with the four
     tensors of ``latent_tensors(layout)`` replaced."""
     out = np.array(flat, dtype=np.float64, copy=True)
     lo = np.asarray(lo, dtype=np.float64).reshape(-1)
-    s = scale_of(np.asarray(rng, dtype=np.float64).reshape(-1))
+    s = scale_of(np.asarray(rng, dtype=np.float64).reshape(-1), levels)
     (we, be), (wd, bd) = latent_tensors(layout)
     z = we[2][0]
     if lo.shape != (z,) or s.shape != (z,) or wd[2][1] != z:
@@ -73,13 +133,14 @@ def fold_flat(flat, layout, lo, rng):
     return out
 
 
-def fold(model, lo, rng):
+def fold(model, lo, rng, levels=255):
     """A COPY of ``model``'s flat parameters (numpy, the model's parameter type, ``model.nparams`` long) with the latent scale
-    folded in; ``model`` itself is not changed.  lo, rng: (z,) float64, the calibrated minimum and range of every latent column."""
+    folded in; ``model`` itself is not changed.  lo, rng: (z,) float64, the calibrated minimum and range of every latent column;
+    levels: the code that the maximum maps to (255 for bytes, 2**b - 1 for b-bit codes)."""
     flat = model.flat[: model.nparams].detach().to("cpu").numpy()
-    return fold_flat(flat, model.layout, lo, rng).astype(flat.dtype)
+    return fold_flat(flat, model.layout, lo, rng, levels).astype(flat.dtype)
 
 
-def unscale(codes, lo, rng):
-    """The latent a code stands for: q / s + lo (float64)."""
-    return widen8(codes).astype(np.float64) / scale_of(rng) + np.asarray(lo, dtype=np.float64)
+def unscale(codes, lo, rng, levels=255):
+    """The latent a code stands for: q / s + lo (float64).  codes: uint8, one per element (unpacked)."""
+    return widen8(codes).astype(np.float64) / scale_of(rng, levels) + np.asarray(lo, dtype=np.float64)

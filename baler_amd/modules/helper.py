@@ -333,7 +333,8 @@ def _derive_sizes(config, data_shape, names_len):
 
 
 def latent_dtype_of(config):
-    """config.latent_dtype -> None | "float16" | "bfloat16" (hostio.parse_latent_dtype; anything else: ValueError)."""
+    """config.latent_dtype -> None | "float16" | "bfloat16" | "uint8" | "uint1" .. "uint7" (hostio.parse_latent_dtype; anything
+    else: ValueError)."""
     return hostio.parse_latent_dtype(getattr(config, "latent_dtype", None))
 
 
@@ -361,8 +362,8 @@ def _check_float16_range(h, flat, feats, out, world):
                          "(float32's range at 8 bits of precision) or leave latent_dtype unset.")
 
 
-def _calibrate_latent8(h, flat, feats, world):
-    """config.latent_dtype = "uint8", first pass: the extrema of every latent column over ALL rows -> (2, z) float64 numpy
+def _calibrate_latent8(h, flat, feats, world, name="uint8"):
+    """config.latent_dtype = "uint8" (or "uint1" .. "uint7": ``name``, for the message), first pass: the extrema of every latent column over ALL rows -> (2, z) float64 numpy
     [min ; range].  Per ROW_BLOCK one float32 encode and one bamd_col_minmax; the blocks' 2 x z doubles are combined on the device,
     the ranks' with one MIN and one MAX all-reduce (exact in any order, so every rank count gives the same scale).  A non-finite
     extremum (a NaN or inf latent: bamd_col_minmax propagates NaN) raises ValueError on every rank, before anything is written."""
@@ -382,7 +383,7 @@ def _calibrate_latent8(h, flat, feats, world):
         scale = np.stack([mm[0], mm[1] - mm[0]])
     if not (np.isfinite(mm).all() and np.isfinite(scale).all()):
         bad = int((~(np.isfinite(mm) & np.isfinite(scale)).all(axis=0)).sum())
-        raise ValueError(f"latent_dtype = \"uint8\": {bad} of {z} latent columns have a non-finite minimum or maximum over this table "
+        raise ValueError(f"latent_dtype = \"{name}\": {bad} of {z} latent columns have a non-finite minimum or maximum over this table "
                          "(a NaN or inf row, or a model that overflows on it), so there is no scale for the codes; no archive is "
                          "written.  Use latent_dtype = \"float16\" / \"bfloat16\" or leave latent_dtype unset.")
     return scale
@@ -427,7 +428,11 @@ def compress(model_path, config):
     ``config.latent_dtype`` = "uint8": two passes.  The first finds the extrema of every latent column (_calibrate_latent8); the map
     of [min, min + range] onto [0, 255] is then folded into the last encoder and the first decoder layer of THIS RUN's copy of the
     parameters (baler_amd.latent8; model.pt is not touched), and the second pass encodes to bytes: 1 byte per code.  The scale is
-    left in ``config.latent_scale`` for the archive; the deltas come from decode() of the bytes on the folded handle."""
+    left in ``config.latent_scale`` for the archive; the deltas come from decode() of the bytes on the folded handle.
+
+    ``config.latent_dtype`` = "uint1" .. "uint7": the same two passes with 2**b - 1 in the place of 255; the second pass writes
+    packed rows of ceil(z * b / 8) bytes (bamd_codeb; baler_amd.latent8.pack_rows states the layout), which every later step
+    -- row blocks, the gather, the archive -- moves as plain byte rows."""
     want_deltas = bool(getattr(config, "save_error_bounded_deltas", False))
     latent_dtype = latent_dtype_of(config)          # (a bad value fails here, before any GPU work)
     rank, world = bdist.rank_world()
@@ -456,13 +461,16 @@ def compress(model_path, config):
     model.eval()
     h = model.handle()
     n_local = flat.shape[0]
-    if latent_dtype == "uint8":
+    bits = hostio.latent_bits(latent_dtype)      # None | 8 ("uint8") | 1 .. 7 (packed rows)
+    packed = bits if bits is not None and bits < 8 else None
+    if bits is not None:
         # the affine map of the codes goes INTO the model of this run (model.pt stays as it is): from here on h emits the latent in
-        # code units [0, 255], and decodes them.  config.latent_scale: what perform_compression writes next to the codes.
-        config.latent_scale = _calibrate_latent8(h, flat, feats, world)
-        model.load_flat(latent8.fold(model, config.latent_scale[0], config.latent_scale[1]))
+        # code units [0, 2**bits - 1], and decodes them.  config.latent_scale: what perform_compression writes next to the codes.
+        config.latent_scale = _calibrate_latent8(h, flat, feats, world, latent_dtype)
+        model.load_flat(latent8.fold(model, config.latent_scale[0], config.latent_scale[1], latent8.levels(bits)))
         h = model.handle()
-    out = torch.empty((n_local, config.latent_space_size), dtype=hostio.LATENT_DTYPES.get(latent_dtype, work_dtype), device=flat.device)
+    width = config.latent_space_size if packed is None else hostio.packed_row_bytes(config.latent_space_size, packed)
+    out = torch.empty((n_local, width), dtype=hostio.LATENT_DTYPES.get(latent_dtype, work_dtype), device=flat.device)
     if want_deltas:
         flags = torch.empty((n_local, n_features), dtype=torch.uint8, device=flat.device)
         deltas = torch.empty((n_local, n_features), dtype=torch.float16, device=flat.device)
@@ -470,22 +478,23 @@ def compress(model_path, config):
     for s in range(0, n_local, ROW_BLOCK):
         e = min(s + ROW_BLOCK, n_local)
         if not want_deltas:
-            h.encode(flat[s:e], features=feats, out=out[s:e])
+            h.encode(flat[s:e], features=feats, out=out[s:e], code_bits=packed)
         else:
             # the side channel compares decode(encode(x)) with the NORMALISED input (helper.py:589-606)
             xn = native.normalize(flat[s:e], feats, out_dtype=work_dtype) if feats is not None else flat[s:e]
-            h.encode(xn, out=out[s:e])
-            flags[s:e], deltas[s:e] = native.error_deltas(xn, h.decode(out[s:e], out_dtype=xn.dtype), config.error_bounded_requirement)
+            h.encode(xn, out=out[s:e], code_bits=packed)
+            flags[s:e], deltas[s:e] = native.error_deltas(xn, h.decode(out[s:e], out_dtype=xn.dtype, code_bits=packed),
+                                                          config.error_bounded_requirement)
         ev = torch.cuda.Event()
         ev.record()
         ready.append((e, ev))
     if latent_dtype == "float16":       # before the gather and the download: an overflowing run fails without moving the codes
         _check_float16_range(h, flat, feats, out, world)
     checked = out
-    if latent_dtype == "uint8" and h.compute_mode in (native.MODE_F16, native.MODE_F16X3):
-        # a byte cannot show a non-finite latent (NaN is stored as 0): the fp16 modes' range check reads the folded handle's float32
+    if bits is not None and h.compute_mode in (native.MODE_F16, native.MODE_F16X3):
+        # a byte (or a packed code) cannot show a non-finite latent (NaN is stored as 0): the fp16 modes' range check reads the folded handle's float32
         # latent instead -- a tiny range makes a large folded weight, which can leave the float16 range where the plain model did not
-        checked = torch.empty(out.shape, dtype=torch.float32, device=out.device)
+        checked = torch.empty((n_local, config.latent_space_size), dtype=torch.float32, device=out.device)
         for s in range(0, n_local, ROW_BLOCK):
             e = min(s + ROW_BLOCK, n_local)
             h.encode(flat[s:e], features=feats, out=checked[s:e])
@@ -591,8 +600,10 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
     normalization_features = loaded["normalization_features"]
     # 16-bit codes are recognised from the ARCHIVE (data.dtype / its latent_dtype key), never from the config
     data, code_dtype = hostio.latent_from_archive(data, loaded.files, lambda k: loaded[k])
-    latent_scale = hostio.latent_scale_from_archive(data, loaded.files, lambda k: loaded[k])      # 8-bit codes only (else None)
-    latent_space_size = data.shape[1]
+    latent_scale = hostio.latent_scale_from_archive(data, loaded.files, lambda k: loaded[k])      # 8-bit and packed codes only (else None)
+    bits = hostio.latent_bits(str(loaded["latent_dtype"])) if latent_scale is not None else None
+    packed = bits if bits is not None and bits < 8 else None      # packed rows: data is (N, ceil(z * bits / 8)) bytes
+    latent_space_size = data.shape[1] if packed is None else latent_scale.shape[1]
     model_dict = torch.load(str(model_path), map_location="cpu")
     number_of_columns = len(model_dict[list(model_dict.keys())[-1]])  # len(de4.bias), helper.py:668-674
 
@@ -605,7 +616,7 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
                                            n_features=number_of_columns, z_dim=latent_space_size)
     model.eval()
     if latent_scale is not None:      # 8-bit codes: this run's copy of the parameters decodes code units (model.pt is not touched)
-        model.load_flat(latent8.fold(model, latent_scale[0], latent_scale[1]))
+        model.load_flat(latent8.fold(model, latent_scale[0], latent_scale[1], latent8.levels(bits)))
     h = model.handle()
     rank, world = bdist.rank_world()
     n_total = data.shape[0]
@@ -628,9 +639,9 @@ def decompress(model_path, input_path, input_path_deltas, input_batch_index, mod
     for s in range(0, hi - lo, ROW_BLOCK):
         e = min(s + ROW_BLOCK, hi - lo)
         if fuse:
-            h.decode(z[s:e], features=r_feats, int_mask=r_mask, out=out[s:e])
+            h.decode(z[s:e], features=r_feats, int_mask=r_mask, out=out[s:e], code_bits=packed)
         else:
-            h.decode(z[s:e], out=out[s:e])
+            h.decode(z[s:e], out=out[s:e], code_bits=packed)
         ev = torch.cuda.Event()
         ev.record()
         ready.append((e, ev))

@@ -16,6 +16,21 @@ LIB_PATH = os.environ.get("BALER_AMD_LIB", os.path.join(_HERE, "libbaler_amd.so"
 F32, F64 = 0, 1
 F16, BF16 = 2, 3        # 16-bit latent codes: the z of bamd_encode / bamd_decode only (include/baler_amd.h, bamd_dtype)
 U8 = 8                  # 8-bit latent codes (bamd_code8): the same two places; rint + clamp to [0, 255] on store, exact widening on load
+
+
+
+def UB(bits):
+    """Code kind of packed ``bits``-bit latent codes, bits = 1 .. 7 (bamd_codeb: BAMD_U1 = 0x101 .. BAMD_U7 = 0x107)."""
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 7:
+        raise NativeError(f"packed latent codes have 1 to 7 bits, got {bits!r}")
+    return 0x100 | bits
+
+
+def packed_row_bytes(z_dim, bits):
+    """Bytes of one packed latent row: ceil(z_dim * bits / 8) (rows are byte-aligned)."""
+    return (int(z_dim) * int(bits) + 7) // 8
+
+
 MODE_F32, MODE_F64, MODE_BF16, MODE_F16 = 0, 1, 2, 3     # MODE_F16: binary16 inference of the 24-column AE, fp32 training
 MODE_F16X3 = 5      # fp32 accuracy from three binary16 MFMA products per tile (24-column AE inference, fp32 training); 4 is not a mode
 MODE_NAMES = {"fp32": MODE_F32, "f32": MODE_F32, "fp64": MODE_F64, "f64": MODE_F64, "bf16": MODE_BF16, "fp16": MODE_F16, "f16": MODE_F16,
@@ -464,27 +479,44 @@ class Handle:
             raise NativeError(f"out has shape {tuple(out.shape)}, expected {(rows, cols)}")
         return out
 
-    def encode(self, x, features=None, out_dtype=None, out=None):
+    def encode(self, x, features=None, out_dtype=None, out=None, code_bits=None):
         """z = encode(x).  out_dtype (or the dtype of ``out``): float32 / float64, or torch.float16 / torch.bfloat16 for 16-bit
         codes -- the round-to-nearest-even conversion of the float32 codes, made on the device by bamd_encode (inside the encode kernel
         for the fp32 register chain, bf16.hip and the layer-wise path; one conversion launch behind a float32 workspace otherwise).
         torch.uint8: 8-bit codes, q = clamp(rint(float32 code), 0, 255) -- workspace and conversion launch for every family; the
-        parameters are expected to carry the latent scale (baler_amd.latent8.fold)."""
+        parameters are expected to carry the latent scale (baler_amd.latent8.fold).
+        code_bits = b (1 .. 7) with torch.uint8: packed b-bit codes, q = clamp(rint(float32 code), 0, 2**b - 1); the result is
+        (n, ceil(z_dim * b / 8)) bytes, each row a little-endian bit string of its codes (baler_amd.latent8.pack_rows).  Without
+        code_bits a uint8 output means one byte per code."""
         x = _dev_tensor(x)
         self._mine(x, features)
-        out = self._out(out, x.shape[0], self.z_dim, out_dtype or x.dtype, x.device)
-        _check(lib().bamd_encode(self._h, _ptr(x), _dt(x), x.shape[0], _ptr(features), _ptr(out), _dt_latent(out),
+        if code_bits is None:
+            out = self._out(out, x.shape[0], self.z_dim, out_dtype or x.dtype, x.device)
+            code = _dt_latent(out)
+        else:
+            code = UB(code_bits)
+            if (out_dtype or torch.uint8) != torch.uint8 or (out is not None and out.dtype != torch.uint8):
+                raise NativeError("packed latent codes (code_bits) are written to a uint8 tensor")
+            out = self._out(out, x.shape[0], packed_row_bytes(self.z_dim, code_bits), torch.uint8, x.device)
+        _check(lib().bamd_encode(self._h, _ptr(x), _dt(x), x.shape[0], _ptr(features), _ptr(out), code,
                                  self._s()), "bamd_encode")
         return out
 
-    def decode(self, z, features=None, int_mask=None, out_dtype=None, out=None):
+    def decode(self, z, features=None, int_mask=None, out_dtype=None, out=None, code_bits=None):
         """out = decode(z).  z may hold float16 / bfloat16 / uint8 codes: they are widened exactly, the result is that of the widened
-        float32 codes bit for bit (default output dtype then: float32)."""
+        float32 codes bit for bit (default output dtype then: float32).  code_bits = b (1 .. 7): z holds packed rows of b-bit
+        codes, uint8 (n, ceil(z_dim * b / 8)), unpacked the same way."""
         z = _dev_tensor(z)
         self._mine(z, features, int_mask)
+        code = _dt_latent(z)
+        if code_bits is not None:
+            code = UB(code_bits)
+            if z.dtype != torch.uint8 or z.dim() != 2 or z.shape[1] != packed_row_bytes(self.z_dim, code_bits):
+                raise NativeError(f"z: packed {code_bits}-bit codes of {self.z_dim} columns are uint8 (n_rows, "
+                                  f"{packed_row_bytes(self.z_dim, code_bits)}), got {z.dtype} {tuple(z.shape)}")
         default = z.dtype if z.dtype in (torch.float32, torch.float64) else torch.float32
         out = self._out(out, z.shape[0], self.dims[-1], out_dtype or default, z.device)
-        _check(lib().bamd_decode(self._h, _ptr(z), _dt_latent(z), z.shape[0], _ptr(features), _ptr(int_mask),
+        _check(lib().bamd_decode(self._h, _ptr(z), code, z.shape[0], _ptr(features), _ptr(int_mask),
                                  _ptr(out), _dt(out), self._s()), "bamd_decode")
         return out
 

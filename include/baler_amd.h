@@ -80,6 +80,25 @@ typedef enum bamd_dtype { BAMD_F32 = 0, BAMD_F64 = 1, BAMD_F16 = 2, BAMD_BF16 = 
  * codes pass through the handle's float32 latent workspace and one row-conversion launch; no encode or decode kernel changes. */
 typedef enum bamd_code8 { BAMD_U8 = 8 } bamd_code8;
 
+/* Packed sub-byte latent codes, b = 1 .. 7 bits each: a third code kind, numbered 0x100 | b (BAMD_UB(b)); "code = bits" would
+ * collide with values that stay refused.  Legal exactly where BAMD_U8 is -- z_dtype of the encode entry point (output) and of
+ * the decode entry point (input); every other dtype argument of every entry point returns BAMD_ERR_INVALID for them, naming the
+ * argument, before anything is launched or written.  0x100, 0x108 and 0x109 name nothing and are refused as well.
+ * Store: v as for BAMD_U8; q = (unsigned) min(max(rint(v), 0), 2^b - 1), round-half-to-even in float32; NaN and -inf give 0,
+ * +inf gives 2^b - 1 (for b = 8 this would be the BAMD_U8 rule).
+ * Layout: the buffer is (n_rows, S) bytes, row-major, S = ceil(z_dim * b / 8).  Code k of a row occupies bits [k b, (k + 1) b)
+ * of that row's bit string; bit i of a row is bit (i mod 8) of the row's byte (i div 8) -- least-significant bit first, the
+ * order of numpy's packbits(bitorder="little").  The unused high bits of a row's last byte are written as zero and ignored on
+ * load.  Rows are byte-aligned on purpose: row chunks, rank slices and row plans stay plain byte ranges (a chunk that starts at
+ * row r starts at byte r * S); the cost is at most 7 bits per row.
+ * Load: float32(q), exact; a decode of packed codes equals the decode of their float32 widening bit for bit, the fused
+ * un-normalise and int-truncation epilogue included.  As for BAMD_U8 the library knows no scale, every family goes through the
+ * float32 latent workspace and one row-conversion launch, and no encode or decode kernel changes. */
+typedef enum bamd_codeb {
+    BAMD_U1 = 0x101, BAMD_U2 = 0x102, BAMD_U3 = 0x103, BAMD_U4 = 0x104, BAMD_U5 = 0x105, BAMD_U6 = 0x106, BAMD_U7 = 0x107
+} bamd_codeb;
+#define BAMD_UB(bits) (0x100 | (bits))      /* bits = 1 .. 7 */
+
 /* arithmetic the Linear layers run in.  F32 = v_mfma_f32_16x16x4_f32 (exact fp32, the parity mode:
  * outputs within 1e-5 rel. of the fp64 reference).  F64 = v_mfma_f64_16x16x4_f64 (long-horizon
  * training parity).  BF16 = v_mfma_f32_16x16x32_bf16 with fp32 accumulation: a THROUGHPUT mode with its own 2e-2 bar.
@@ -317,13 +336,14 @@ int bamd_renormalize(const void *x, int dtype, int64_t n_rows, int n_cols, const
  * rounded as described at bamd_dtype; the conversion is part of the encode launch for the fp32 register-chain, bf16 and
  * layer-wise kernels, and one row-conversion launch behind a float32 workspace for the wide-layer kernels, the fp64 chain,
  * FPGA_prototype_model and PJ_Conv_AE), or BAMD_U8 for 8-bit codes (1 byte per element, see bamd_code8: float32 workspace and
- * one row-conversion launch for every family).  x_dtype is BAMD_F32 or BAMD_F64. */
+ * one row-conversion launch for every family), or BAMD_U1 .. BAMD_U7 for packed sub-byte codes (z is then (n_rows, S) bytes,
+ * S = ceil(z_dim * b / 8), see bamd_codeb; the same route).  x_dtype is BAMD_F32 or BAMD_F64. */
 int bamd_encode(bamd_handle *h, const void *x, int x_dtype, int64_t n_rows, const double *features,
                 void *z, int z_dtype, void *stream);
 /* Replaces: AE.decode (models.py:147-152) as driven by helper.decompress (helper.py:700-723), with
  * the optional un-normalise + int-column truncation epilogue of baler.py:420-435 fused in when
  * features != NULL (int_mask may still be NULL).  z_dtype may be BAMD_F16 / BAMD_BF16: the codes are widened exactly on load and
- * the result is bit-identical to decoding the widened float32 codes; BAMD_U8 codes likewise.  out_dtype is BAMD_F32 or BAMD_F64. */
+ * the result is bit-identical to decoding the widened float32 codes; BAMD_U8 codes and packed BAMD_U1 .. BAMD_U7 rows likewise.  out_dtype is BAMD_F32 or BAMD_F64. */
 int bamd_decode(bamd_handle *h, const void *z, int z_dtype, int64_t n_rows, const double *features,
                 const uint8_t *int_mask, void *out, int out_dtype, void *stream);
 /* Replaces: AE.forward (models.py:154-156) + utils.mse_sum_loss_l1(validate=True)
