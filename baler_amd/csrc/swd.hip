@@ -10,6 +10,9 @@
 //               (value, row) pairs for z and of the values for the prior, per-projection loss partial and
 //               the gradient w.r.t. the projected values scattered back to row order: G[s][row].
 //   swd_dz_k    dz[row][k] = sum_s G[s][row] * P[s][k] in a fixed order (no atomics: reproducible).
+// The (value, row) pairs are sorted in a TOTAL order (bitonic_cmpx_total, bitonic.hpp): NaN last, equal values by row, the NaN
+// padding (rows n .. m-1) after every real element.  So ranks 0 .. n-1 hold exactly the rows 0 .. n-1 whatever z holds, and the
+// scatter G[s][row] below stays inside the projection's row of G and writes all of it (tests/test_gpu_swd_edge.py).
 // Batches above 4096 rows (CFD_project_animation_config.py:19: batch_size = 6000) run the same bitonic network in passes
 // through global memory (swd_project_k / swd_local_k / swd_global_k / swd_finish_k below).
 #include "bamd_internal.hpp"
@@ -30,7 +33,7 @@ __global__ void __launch_bounds__(256) swd_sort_k(const T *__restrict__ z, const
     const int s = blockIdx.x, tid = threadIdx.x;
     const T *P = proj + (int64_t)s * d;
     for (int i = tid; i < m; i += 256) {
-        T a = pos_inf<T>(), b = pos_inf<T>();
+        T a = nan_key<T>(), b = nan_key<T>();       // padding: after every real key, a real NaN included (bitonic.hpp)
         if (i < n) {
             a = (T)0; b = (T)0;
             for (int k = 0; k < d; ++k) {
@@ -42,7 +45,7 @@ __global__ void __launch_bounds__(256) swd_sort_k(const T *__restrict__ z, const
     }
     __syncthreads();
     bitonic_network(m, 0, 2, m, tid, 256,
-                    [&](int lo, int hi, bool up) { bitonic_cmpx(av[lo], av[hi], ai[lo], ai[hi], up); bitonic_cmpx(bv[lo], bv[hi], up); },
+                    [&](int lo, int hi, bool up) { bitonic_cmpx_total(av[lo], av[hi], ai[lo], ai[hi], up); bitonic_cmpx_total(bv[lo], bv[hi], up); },
                     [] { __syncthreads(); });
     double acc = 0.0;
     for (int i = tid; i < n; i += 256) {
@@ -66,7 +69,7 @@ __global__ void __launch_bounds__(256) swd_project_k(const T *__restrict__ z, co
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
     const T *P = proj + (int64_t)s * d;
-    T a = pos_inf<T>(), b = pos_inf<T>();
+    T a = nan_key<T>(), b = nan_key<T>();       // padding: after every real key, a real NaN included (bitonic.hpp)
     if (i < n) {
         a = (T)0; b = (T)0;
         for (int k = 0; k < d; ++k) {
@@ -88,7 +91,7 @@ __global__ void __launch_bounds__(256) swd_local_k(T *__restrict__ AV, T *__rest
     for (int i = threadIdx.x; i < kSwdChunk; i += 256) { av[i] = AV[base + i]; bv[i] = BV[base + i]; ai[i] = AI[base + i]; }
     __syncthreads();
     bitonic_network(kSwdChunk, g0, k_lo, k_hi, threadIdx.x, 256,
-                    [&](int lo, int hi, bool up) { bitonic_cmpx(av[lo], av[hi], ai[lo], ai[hi], up); bitonic_cmpx(bv[lo], bv[hi], up); },
+                    [&](int lo, int hi, bool up) { bitonic_cmpx_total(av[lo], av[hi], ai[lo], ai[hi], up); bitonic_cmpx_total(bv[lo], bv[hi], up); },
                     [] { __syncthreads(); });
     for (int i = threadIdx.x; i < kSwdChunk; i += 256) { AV[base + i] = av[i]; BV[base + i] = bv[i]; AI[base + i] = ai[i]; }
 }
@@ -99,8 +102,8 @@ __global__ void __launch_bounds__(256) swd_global_k(T *__restrict__ AV, T *__res
     const int64_t base = (int64_t)blockIdx.y * m;
     const int lo = bitonic_lo(t, j), hi = lo + j;
     const bool up = bitonic_up(lo, k);
-    bitonic_cmpx(AV[base + lo], AV[base + hi], AI[base + lo], AI[base + hi], up);
-    bitonic_cmpx(BV[base + lo], BV[base + hi], up);
+    bitonic_cmpx_total(AV[base + lo], AV[base + hi], AI[base + lo], AI[base + hi], up);
+    bitonic_cmpx_total(BV[base + lo], BV[base + hi], up);
 }
 // per projection: loss partial + gradient w.r.t. the projected values, scattered back to row order
 template <typename T>

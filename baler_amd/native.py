@@ -252,7 +252,8 @@ def emd_rows(x, recon):
 
 
 def swd(z, prior, proj, reg_weight):
-    """utils.compute_swd forward + backward: -> (loss float64[1], dz like z).  z, prior (n, d); proj (s, d) unit rows."""
+    """utils.compute_swd forward + backward: -> (loss float64[1], dz like z).  z, prior (n, d); proj (s, d) unit rows.
+    A stable sort: NaN last, ties by row.  A NaN in z gives a NaN loss and NaN in that row of dz alone (include/baler_amd.h)."""
     z, prior, proj = _dev_tensor(z), _dev_tensor(prior), _dev_tensor(proj)
     if not (z.dtype == prior.dtype == proj.dtype) or z.shape != prior.shape or proj.shape[1] != z.shape[1]:
         raise NativeError("swd: z/prior (n, d) and proj (s, d) must share dtype and latent size")

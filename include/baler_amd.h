@@ -378,7 +378,14 @@ int bamd_fwd_bwd_latent(bamd_handle *h, const void *x, int x_dtype, int64_t n_ro
  * the batch; *loss_out = reg_weight * mean_{s,k} (sort(z.P_s)_k - sort(prior.P_s)_k)^2 (float64), and
  * dz_out (n_rows, z_dim, `dtype`) = d loss / d z.  The random draws are the caller's (the reference
  * takes them from torch's global generator, utils.py:59,79-91).  2 <= n_rows <= 1048576 (up to 4096 rows one workgroup per
- * projection sorts in LDS; larger batches, e.g. CFD_project_animation's 6000, take passes through global memory). */
+ * projection sorts in LDS; larger batches, e.g. CFD_project_animation's 6000, take passes through global memory).
+ * The order of the sort is total, the one of a stable sort (numpy.argsort(kind="stable")): a NaN key sorts last, after +inf, and equal
+ * keys -- identical latent rows, all NaNs -- are ordered by row, so each row of a tie group meets its own prior value and the result
+ * is the same bits on every call.  Non-finite inputs propagate as IEEE arithmetic has them and never move a store: *loss_out is NaN
+ * when a projection of z or of prior is NaN (a NaN anywhere in z, prior or proj), the rows of dz_out whose z holds a NaN are NaN,
+ * and every other row is what the same arithmetic gives in float64 (a NaN in prior reaches the row at the top rank of each
+ * projection; a NaN in proj[s] makes that projection, and with it all of dz_out, NaN).  +-inf in z sort as values: the loss is +inf
+ * (NaN where +inf meets +inf of the prior at the same rank), that row of dz_out is non-finite, the others are finite. */
 int bamd_swd(const void *z, const void *prior, const void *proj, int dtype, int64_t n_rows, int z_dim,
              int n_proj, double reg_weight, double *loss_out, void *dz_out, void *stream);
 /* Replaces: torch.optim.Adam.step + zero_grad (training.py:68,95,266) on the flat buffers, and
