@@ -1,6 +1,7 @@
 // Column residual / response statistics of a (before, after) table pair: the data path of plotting.plot_1D
 // (plotting.py:101-239).  Two HBM-streaming passes, each reading each table once: bamd_column_moments (counts, sums,
-// extrema) and bamd_column_hist (four histograms per column with numpy's bin rule).  gfx950 only.
+// extrema) and bamd_column_hist (four histograms per column with numpy's bin rule; the residual's bins may differ per column).
+// gfx950 only.
 #include "bamd_internal.hpp"
 
 namespace bamd {
@@ -333,6 +334,77 @@ __global__ void __launch_bounds__(1024) colhist_k(const T *__restrict__ before, 
     }
 }
 
+// ---- pass B': the residual histogram with per-column, unevenly spaced edges (bamd_column_hist with n_ed < 0) -----------------------
+// The edges of one call may run from -1e-3 through the subnormals to +1e-3 (a selection bracket in key space, baler_amd/colbox.py),
+// so there is no scale to guess a bin with: the bin is found by bisection over the column's edges in LDS, values and edges compared
+// as float64 and no arithmetic on an edge -- a first edge of -inf or a last one of +inf needs no special case.  np.histogram's rule
+// as in find_bin.  -> bin, or -1.
+__device__ __forceinline__ int bisect_bin(double v, const double *e, int nb) {
+    if (!(v >= e[0] && v <= e[nb])) return -1;
+    int lo = 0, hi = nb;                // e[lo] <= v, and v < e[hi] or hi == nb
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (v >= e[mid]) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// LDS: [cols_per_group][n_edges] edges, then [cols_per_group][n_edges - 1] 32-bit counters: the walk, the column groups of blockIdx.y
+// and the flush of colhist_k.
+template <typename T, int V>
+__global__ void __launch_bounds__(1024) colhist_percol_k(const T *__restrict__ before, const T *__restrict__ after, int64_t n, int c,
+                                                         int cut_col, double cut, int Tn, int rows_per_tile, int64_t tiles,
+                                                         const double *__restrict__ edges, int n_edges,
+                                                         unsigned long long *__restrict__ counts, int cols_per_group) {
+    extern __shared__ double lds[];
+    const int t = threadIdx.x;
+    const int col0 = blockIdx.y * cols_per_group;
+    const int ncol = min(cols_per_group, c - col0);
+    const int nb = n_edges - 1;
+    double *e_col = lds;                                                                           // [ncol][n_edges]
+    unsigned *cnts = reinterpret_cast<unsigned *>(e_col + (size_t)cols_per_group * n_edges);      // [ncol][nb]
+    for (int i = t; i < ncol * n_edges; i += 1024) e_col[i] = edges[(int64_t)col0 * n_edges + i];
+
+    const int64_t total = n * c;
+    Slots<V> sl;
+    sl.init(t, c);
+    int lc[V];                      // the slot's column inside this group, or -1
+#pragma unroll
+    for (int j = 0; j < V; ++j) lc[j] = (t < Tn && sl.col[j] >= col0 && sl.col[j] < col0 + ncol) ? sl.col[j] - col0 : -1;
+    const int ncnt = ncol * nb;
+    for (int64_t q0 = blockIdx.x; q0 < tiles; q0 += kFlushTiles * gridDim.x) {
+        for (int i = t; i < ncnt; i += 1024) cnts[i] = 0u;
+        __syncthreads();            // (the first round: the edges are in place too)
+        int64_t q_end = q0 + kFlushTiles * gridDim.x;
+        q_end = q_end < tiles ? q_end : tiles;
+        if (t < Tn) {
+            for (int64_t q = q0; q < q_end; q += gridDim.x) {
+                const int64_t e = (q * Tn + t) * V;
+                if (e >= total) break;
+                T b[V], a[V];
+                load_vec<T, V>(before, e, total, b);
+                load_vec<T, V>(after, e, total, a);
+                bool keep[V];
+                row_keep<T, V>(before, q * rows_per_tile, sl, n, c, cut_col, cut, keep);
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    if (!keep[j] || lc[j] < 0) continue;
+                    const T rd = a[j] - b[j];
+                    const int k = bisect_bin((double)rd, e_col + lc[j] * n_edges, nb);
+                    if (k >= 0) atomicAdd(cnts + lc[j] * nb + k, 1u);
+                }
+            }
+        }
+        __syncthreads();
+        for (int i = t; i < ncnt; i += 1024) {
+            const unsigned v = cnts[i];
+            if (v) atomicAdd(counts + (int64_t)col0 * nb + i, (unsigned long long)v);      // [col0 + i / nb][i % nb]
+        }
+        __syncthreads();
+    }
+}
+
 bool aligned16(const void *a, const void *b) { return (((uintptr_t)a | (uintptr_t)b) & 15u) == 0; }
 
 int check_tables(const char *fn, int dtype, int n_cols, int cut_col) {
@@ -412,10 +484,16 @@ int bamd_column_hist(const void *before, const void *after, int dtype, int64_t n
         BAMD_REQUIRE(counts_resp, "edges_resp without counts_resp");
         ha.edges_resp = edges_resp; ha.n_er = n_er; ha.counts_resp = (unsigned long long *)counts_resp;
     }
+    int n_pc = 0;                   // n_ed < 0: edges_resid is (n_cols, n_pc), one edge array per column, and has a launch of its own
     if (edges_resid) {
-        BAMD_REQUIRE(n_ed >= 2 && n_ed <= kMaxEdges, "edges_resid needs 2 .. 1025 edges");
+        BAMD_REQUIRE((n_ed >= 2 && n_ed <= kMaxEdges) || (n_ed <= -2 && n_ed >= -kMaxEdges),
+                     "edges_resid needs 2 .. 1025 edges (n_ed), or -n_ed = 2 .. 1025 edges per column (n_ed < 0)");
         BAMD_REQUIRE(counts_resid, "edges_resid without counts_resid");
-        ha.edges_resid = edges_resid; ha.n_ed = n_ed; ha.counts_resid = (unsigned long long *)counts_resid;
+        if (n_ed > 0) {
+            ha.edges_resid = edges_resid; ha.n_ed = n_ed; ha.counts_resid = (unsigned long long *)counts_resid;
+        } else {
+            n_pc = -n_ed;
+        }
     }
     if (edges_val) {
         BAMD_REQUIRE(n_ev >= 2 && n_ev <= kMaxEdges, "edges_val needs 2 .. 1025 edges per column");
@@ -428,6 +506,7 @@ int bamd_column_hist(const void *before, const void *after, int dtype, int64_t n
     if (!accumulate) {
         if (ha.n_er) BAMD_HIP(hipMemsetAsync(counts_resp, 0, (size_t)c * (n_er - 1) * sizeof(int64_t), s));
         if (ha.n_ed) BAMD_HIP(hipMemsetAsync(counts_resid, 0, (size_t)c * (n_ed - 1) * sizeof(int64_t), s));
+        if (n_pc) BAMD_HIP(hipMemsetAsync(counts_resid, 0, (size_t)c * (n_pc - 1) * sizeof(int64_t), s));
         if (ha.n_ev) {
             BAMD_HIP(hipMemsetAsync(counts_before, 0, (size_t)c * (n_ev - 1) * sizeof(int64_t), s));
             BAMD_HIP(hipMemsetAsync(counts_after, 0, (size_t)c * (n_ev - 1) * sizeof(int64_t), s));
@@ -439,11 +518,44 @@ int bamd_column_hist(const void *before, const void *after, int dtype, int64_t n
     BAMD_HIP(hipGetDevice(&dev));
     BAMD_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
     BAMD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    // LDS of a workgroup: the two shared edge arrays, then per column its value edges and its counters
+    const int V = aligned16(before, after) ? (dtype == BAMD_F64 ? 2 : 4) : 1;
+    const Walk w = make_walk(1024, c, V, n_rows);
+    const int64_t want = w.tiles < (int64_t)(cus > 0 ? cus : 256) ? w.tiles : (int64_t)(cus > 0 ? cus : 256);
+    // both LDS checks come before the first launch: every refusal comes before the first count is added
+    const bool shared = ha.n_er || ha.n_ed || ha.n_ev;
     const size_t shared_bytes = (size_t)(ha.n_er + ha.n_ed) * sizeof(double);
     const int bins_per_col = (ha.n_er ? ha.n_er - 1 : 0) + (ha.n_ed ? ha.n_ed - 1 : 0) + 2 * (ha.n_ev ? ha.n_ev - 1 : 0);
     const size_t col_bytes = (size_t)ha.n_ev * sizeof(double) + (size_t)bins_per_col * sizeof(unsigned);
-    BAMD_REQUIRE((size_t)lds_max >= shared_bytes + col_bytes, "the device's LDS does not hold one column's histograms");
+    const size_t pc_col_bytes = (size_t)n_pc * sizeof(double) + (size_t)(n_pc ? n_pc - 1 : 0) * sizeof(unsigned);
+    BAMD_REQUIRE(!shared || (size_t)lds_max >= shared_bytes + col_bytes, "the device's LDS does not hold one column's histograms");
+    BAMD_REQUIRE(!n_pc || (size_t)lds_max >= pc_col_bytes, "the device's LDS does not hold one column's histogram");
+    if (n_pc) {
+        // LDS of a workgroup: per column its edges and its counters (12 KiB at 1025 edges)
+        const size_t col_bytes = pc_col_bytes;
+        int cpg = (int)((size_t)lds_max / col_bytes);
+        cpg = cpg > c ? c : cpg;
+        const int groups = (c + cpg - 1) / cpg;
+        cpg = (c + groups - 1) / groups;                  // even column ranges
+        const size_t lds_bytes = (size_t)cpg * col_bytes;
+        const dim3 grid((unsigned)want, (unsigned)groups);
+#define BAMD_LAUNCH_PERCOL(TT, VV)                                                                                                 \
+    do {                                                                                                                           \
+        BAMD_HIP(hipFuncSetAttribute((const void *)colhist_percol_k<TT, VV>, hipFuncAttributeMaxDynamicSharedMemorySize,           \
+                                     (int)lds_bytes));                                                                             \
+        hipLaunchKernelGGL((colhist_percol_k<TT, VV>), grid, dim3(1024), lds_bytes, s, (const TT *)before, (const TT *)after,      \
+                           n_rows, c, cut_col, cut, w.T, w.rows_per_tile, w.tiles, edges_resid, n_pc,                              \
+                           (unsigned long long *)counts_resid, cpg);                                                               \
+    } while (0)
+        if (dtype == BAMD_F64) {
+            if (V == 2) BAMD_LAUNCH_PERCOL(double, 2); else BAMD_LAUNCH_PERCOL(double, 1);
+        } else {
+            if (V == 4) BAMD_LAUNCH_PERCOL(float, 4); else BAMD_LAUNCH_PERCOL(float, 1);
+        }
+#undef BAMD_LAUNCH_PERCOL
+        BAMD_HIP(hipGetLastError());
+        if (!shared) return BAMD_OK;                      // (the shared-edge histograms of the same call: the launch below)
+    }
+    // LDS of a workgroup: the two shared edge arrays, then per column its value edges and its counters
     int cpg = (int)(((size_t)lds_max - shared_bytes) / col_bytes);
     cpg = cpg > c ? c : cpg;
     const int groups = (c + cpg - 1) / cpg;
@@ -451,9 +563,6 @@ int bamd_column_hist(const void *before, const void *after, int dtype, int64_t n
     ha.cols_per_group = cpg;
     const size_t lds_bytes = shared_bytes + (size_t)cpg * col_bytes;
 
-    const int V = aligned16(before, after) ? (dtype == BAMD_F64 ? 2 : 4) : 1;
-    const Walk w = make_walk(1024, c, V, n_rows);
-    const int64_t want = w.tiles < (int64_t)(cus > 0 ? cus : 256) ? w.tiles : (int64_t)(cus > 0 ? cus : 256);
     const dim3 grid((unsigned)want, (unsigned)groups);
 #define BAMD_LAUNCH_HIST(TT, VV)                                                                                                   \
     do {                                                                                                                           \

@@ -17,6 +17,7 @@ import torch
 
 sys.path.append(os.getcwd())
 
+from .. import colbox
 from .. import dist as bdist
 from .. import hostio
 from .. import latent8
@@ -705,6 +706,12 @@ def report_cut(config, n_cols):
     return REPORT_CUT if n_cols > 3 else None
 
 
+def report_kernel_cut(cut, dtype):
+    """The cut as the kernels take it.  numpy compares a float32 column with the Python float in float32 (plotting.py:72), the
+    kernels compare as float64: the threshold rounded to the table's dtype makes the two agree on every row."""
+    return None if cut is None else (int(cut[0]), float(np.dtype(dtype).type(cut[1])))
+
+
 def report_chunk_rows(config, row_bytes):
     """Rows per device chunk of the report: config.report_chunk_rows, else what fills one of hostio's staging buffers."""
     rows = getattr(config, "report_chunk_rows", None)
@@ -723,6 +730,9 @@ def column_report(config, output_path, verbose=False):
     before and after histograms with the reference's bins.  Both tables stream through the GPU in row chunks, twice: moments,
     then -- the value bins come from the before + after extrema -- histograms; the tables never have to fit on the device.
     Under data parallelism each rank takes a contiguous row slice; sums and counts are SUM-, extrema MIN- / MAX-all-reduced.
+    config.report_box (default True) adds the box-and-whisker statistics of the residual (box_q1, box_med, box_q3, box_whislo,
+    box_whishi, box_edge: matplotlib's boxplot_stats, plotting.py:76-98) by exact selection, a few more sweeps; the chunks stay on the
+    device across them when the rank's two slices fit in config.report_box_resident_mb (default 1024) MB, else they stream again.
     Returns the dict that rank 0 also writes to output/plotting/column_stats.npz."""
     check_report(config)
     device = get_device()
@@ -735,6 +745,7 @@ def column_report(config, output_path, verbose=False):
     n, c = before.shape
     cut = report_cut(config, c)
     t_dtype, h_dtype = hostio._device_dtype(np.result_type(before.dtype, after.dtype))
+    shown_cut, cut = cut, report_kernel_cut(cut, h_dtype)
     lo, hi = bdist.shard_rows(n, rank, world)
     chunk = report_chunk_rows(config, 2 * c * np.dtype(h_dtype).itemsize)
 
@@ -773,11 +784,30 @@ def column_report(config, output_path, verbose=False):
     if world > 1:
         for t in counts.values():
             bdist.allreduce_sum(t)
-    result = {"names": names, "cut": np.array(cut if cut is not None else (-1, 0.0), dtype=np.float64)}
+    result = {"names": names, "cut": np.array(shown_cut if shown_cut is not None else (-1, 0.0), dtype=np.float64)}
     result.update(stats)
     result.update(edges_response=e_resp, edges_residual=e_resid, edges_value=e_val,
                   counts_response=counts["resp"].cpu().numpy(), counts_residual=counts["resid"].cpu().numpy(),
                   counts_before=counts["before"].cpu().numpy(), counts_after=counts["after"].cpu().numpy())
+
+    # the box-and-whisker page (plotting.py:76-98): exact order statistics of the residual by bracket descent (colbox.py); every
+    # round is one more sweep of bamd_column_hist with per-column edges, its int64 counts SUM-all-reduced
+    box = None
+    if getattr(config, "report_box", True):
+        mine = 2 * (hi - lo) * c * np.dtype(h_dtype).itemsize
+        resident = list(chunks()) if mine <= float(getattr(config, "report_box_resident_mb", 1024)) * 2 ** 20 else None
+
+        def hist(edges):
+            d_edges = dev(edges)
+            got = native.column_hist(empty, empty, edges_resid=d_edges, cut=cut)
+            for b_dev, a_dev in (resident if resident is not None else chunks()):
+                native.column_hist(b_dev, a_dev, edges_resid=d_edges, cut=cut, out=got)
+            if world > 1:
+                bdist.allreduce_sum(got["resid"])
+            return got["resid"].cpu().numpy()
+
+        box, box_info = colbox.box_stats(stats["count"], stats["resid_min"], stats["resid_max"], hist, h_dtype)
+        result.update(box)
     if rank == 0:
         os.makedirs(os.path.join(output_path, "plotting"), exist_ok=True)
         np.savez(os.path.join(output_path, "plotting", "column_stats.npz"), **result)
@@ -786,4 +816,10 @@ def column_report(config, output_path, verbose=False):
             print(f"{str(names[k]).split('.')[-1]}: residual mean {stats['resid_mean'][k]:.6g} RMS {stats['resid_rms'][k]:.6g} "
                   f"min {stats['resid_min'][k]:.6g} max {stats['resid_max'][k]:.6g}; response mean {stats['resp_mean'][k]:.4g} % "
                   f"RMS {stats['resp_rms'][k]:.4g} %")
+        if box is not None:
+            print(f"=== Box and whisker === ({box_info['rounds']} sweeps, {'resident' if resident is not None else 'streamed'}; "
+                  f"x axis half-width {float(box['box_edge']):.6g})")
+            for k in range(c):
+                print(f"{str(names[k]).split('.')[-1]}: q1 {box['box_q1'][k]:.6g} median {box['box_med'][k]:.6g} q3 {box['box_q3'][k]:.6g} "
+                      f"whiskers {box['box_whislo'][k]:.6g} .. {box['box_whishi'][k]:.6g}")
     return result

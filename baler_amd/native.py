@@ -359,23 +359,27 @@ def column_moments(before, after, cut=None, out=None):
 def column_hist(before, after, edges_resp=None, edges_resid=None, edges_val=None, cut=None, out=None):
     """bamd_column_hist: np.histogram with explicit bins of the response, the residual, ``before`` and ``after`` of every column.
     edges_resp (n_er,), edges_resid (n_ed,), edges_val (c, n_ev): float64 device tensors, or None to skip that histogram.
+    edges_resid may also be (c, n_ed): one edge array per column, which need not be evenly spaced and may begin with -inf and
+    end with +inf (the C ABI's n_ed < 0; baler_amd/colbox.py selects order statistics with it).
     -> dict of int64 device tensors "resp" (c, n_er - 1), "resid" (c, n_ed - 1), "before" and "after" (c, n_ev - 1) for the
     histograms asked for.  ``out`` (such a dict from an earlier call): the counts of this call's rows are added to it."""
     before, after = _table_pair("column_hist", before, after)
     n, c = before.shape
     accumulate = out is not None
     res = dict(out) if accumulate else {}
-    ptr, cnt = {}, {}
+    ptr, cnt, sign = {}, {}, {"resid": 1}
     for key, e, names in (("resp", edges_resp, ("resp",)), ("resid", edges_resid, ("resid",)), ("val", edges_val, ("before", "after"))):
         if e is None:
             ptr[key], cnt[key] = None, 0
             continue
         e = _dev_tensor(e)
-        want_dim = 2 if key == "val" else 1
-        if e.dtype != torch.float64 or e.dim() != want_dim or (key == "val" and e.shape[0] != c):
-            raise NativeError(f"column_hist: edges_{key} must be float64 of shape " + ("(n_cols, n_edges)" if key == "val" else "(n_edges,)"))
+        want_dim = (2,) if key == "val" else ((1, 2) if key == "resid" else (1,))
+        if e.dtype != torch.float64 or e.dim() not in want_dim or (e.dim() == 2 and e.shape[0] != c):
+            raise NativeError(f"column_hist: edges_{key} must be float64 of shape " +
+                              {"val": "(n_cols, n_edges)", "resid": "(n_edges,) or (n_cols, n_edges)", "resp": "(n_edges,)"}[key])
         _same_device("column_hist", before, e)
         ptr[key], cnt[key] = e, int(e.shape[-1])
+        sign[key] = -1 if key == "resid" and e.dim() == 2 else 1       # n_ed < 0: per-column residual edges
         for nm in names:
             if not accumulate:
                 res[nm] = torch.empty((c, max(cnt[key] - 1, 0)), dtype=torch.int64, device=before.device)
@@ -385,7 +389,7 @@ def column_hist(before, after, edges_resp=None, edges_resid=None, edges_val=None
     with torch.cuda.device(before.device):
         _check(lib().bamd_column_hist(_ptr(before), _ptr(after), _dt(before), n, c, cut_col, cut_val,
                                       _ptr(ptr["resp"]), cnt["resp"], _ptr(res.get("resp")),
-                                      _ptr(ptr["resid"]), cnt["resid"], _ptr(res.get("resid")),
+                                      _ptr(ptr["resid"]), sign["resid"] * cnt["resid"], _ptr(res.get("resid")),
                                       _ptr(ptr["val"]), cnt["val"], _ptr(res.get("before")), _ptr(res.get("after")),
                                       int(accumulate), _stream(before)), "bamd_column_hist")
     return res

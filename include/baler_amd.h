@@ -502,7 +502,13 @@ int bamd_column_moments(const void *before, const void *after, int dtype, int64_
  * device memory, (n_cols, edges - 1).  numpy's rule for explicit bins: bin k holds edges[k] <= v < edges[k+1], the last bin also
  * v == edges[-1]; NaN and values outside [edges[0], edges[-1]] are not counted; values are compared as float64.
  * accumulate != 0: the counts of this call's rows are added to counts_*; otherwise they are overwritten.  Integer sums: the
- * result does not depend on any order.  n_rows = 0: BAMD_OK (counts zeroed, or left alone). */
+ * result does not depend on any order.  n_rows = 0: BAMD_OK (counts zeroed, or left alone).
+ * n_ed < 0: per-column residual bins.  edges_resid is then (n_cols, -n_ed) float64, one strictly increasing edge array per
+ * column, and counts_resid is (n_cols, -n_ed - 1); -n_ed is 2 .. 1025 (n_ed = -1 and n_ed < -1025: BAMD_ERR_INVALID).  The
+ * edges need not be evenly spaced (the bin is found by bisection, values and edges compared as float64), the first edge may be
+ * -inf and the last +inf.  The bin rule, the row cut, accumulate and n_rows = 0 are as above; n_er and n_ev keep their meaning,
+ * and the other histograms of the same call give the counts that a call of their own gives.  (Exact order statistics of the
+ * residual -- the box-and-whisker quartiles of plotting.plot_box_and_whisker -- are selected with it: baler_amd/colbox.py.) */
 int bamd_column_hist(const void *before, const void *after, int dtype, int64_t n_rows, int n_cols, int cut_col, double cut,
                      const double *edges_resp, int n_er, int64_t *counts_resp, const double *edges_resid, int n_ed,
                      int64_t *counts_resid, const double *edges_val, int n_ev, int64_t *counts_before, int64_t *counts_after,
