@@ -197,10 +197,14 @@ def perform_decompression(output_path, config, verbose: bool):
 
 
 def perform_report(output_path, config, verbose: bool):
-    """The numbers behind the reference's plot mode for 1-D data (plotting.plot_1D, plotting.py:101-239) -> output/plotting/column_stats.npz."""
-    helper.check_report(config)        # before any GPU work
+    """The numbers behind the reference's plot mode for 1-D data (plotting.plot_1D, plotting.py:101-239) -> output/plotting/column_stats.npz;
+    for 2-D data with config.report_frames = True those behind plotting.plot_2D (plotting.py:370-437) -> output/plotting/frame_stats.npz."""
     start = time.time()
-    helper.column_report(config, output_path, verbose)
+    if helper.report_frames_on(config):
+        helper.frame_report(config, output_path, verbose)
+    else:
+        helper.check_report(config)        # before any GPU work
+        helper.column_report(config, output_path, verbose)
     if bdist.rank_world()[0] == 0:
         print("Report took:", f"{(time.time() - start) / 60:.3} minutes")
 

@@ -116,7 +116,9 @@ def create_default_config(workspace_name: str, project_name: str) -> str:
         ("convert_to_blocks", "False"),
     ]
     body = "\n".join(f"    c.{k:<30} = {v}" for k, v in lines)
-    return f"\n# === Configuration options ===\n\ndef set_config(c):\n{body}\n"
+    notes = ("    # --mode report with data_dimension = 2 is opt-in (per-frame and per-pixel statistics, output/plotting/frame_stats.npz):\n"
+             "    # c.report_frames = True; c.report_diff = True also stores the difference images; c.report_chunk_rows = frames per device chunk\n")
+    return f"\n# === Configuration options ===\n\ndef set_config(c):\n{body}\n{notes}"
 
 
 def model_init(model_name: str):
@@ -721,7 +723,8 @@ def report_chunk_rows(config, row_bytes):
 def check_report(config):
     if config.data_dimension != 1:
         raise NotImplementedError("--mode report serves data_dimension = 1 (plotting.plot_1D); plotting.plot_2D has no native "
-                                  "path: run the reference's plot mode on the artefacts")
+                                  "path: run the reference's plot mode on the artefacts, or set c.report_frames = True for the "
+                                  "per-frame and per-pixel statistics behind its pages (helper.frame_report)")
 
 
 def column_report(config, output_path, verbose=False):
@@ -822,4 +825,96 @@ def column_report(config, output_path, verbose=False):
             for k in range(c):
                 print(f"{str(names[k]).split('.')[-1]}: q1 {box['box_q1'][k]:.6g} median {box['box_med'][k]:.6g} q3 {box['box_q3'][k]:.6g} "
                       f"whiskers {box['box_whislo'][k]:.6g} .. {box['box_whishi'][k]:.6g}")
+    return result
+
+
+# ---- --mode report for 2-D data: the data path of plotting.plot_2D, opt-in with config.report_frames -------------------------------
+def report_frames_on(config):
+    return config.data_dimension == 2 and bool(getattr(config, "report_frames", False))
+
+
+def _frame_tables(config, output_path):
+    """The two host arrays of the 2-D report (memory maps where the archives store them), `after` viewed in `before`'s shape; every
+    shape refusal, before any GPU work."""
+    if config.data_dimension != 2:
+        raise ValueError(f"frame_report serves data_dimension = 2, not {config.data_dimension} (1-D data: column_report)")
+    before = hostio.open_npz_array(config.input_path, "data")
+    after = hostio.open_npz_array(os.path.join(output_path, "decompressed_output", "decompressed.npz"), "data")
+    ok = before.ndim >= 2 and after.ndim >= 1 and before.shape[0] == after.shape[0]
+    elems = int(np.prod(before.shape[1:])) if before.ndim >= 2 else 0
+    if not ok or elems < 1 or after.size != before.shape[0] * elems:
+        raise ValueError(f"report: input {tuple(before.shape)} must be frames (n, ...) and decompressed {tuple(after.shape)} must hold as "
+                         "many frames of as many elements each")
+    # PJ_Conv_AE writes (N, 1, 28, 28), a block run may leave blocks or flat rows: plot_2D reshapes too (plotting.py:388-391)
+    return before, after.reshape(before.shape)
+
+
+def frame_report(config, output_path, verbose=False):
+    """The data path of plotting.plot_2D (plotting.py:370-437) on the device, for every frame: the colour scale vmin / vmax of its
+    three panels and the difference image d = before - after behind the third, plus per-frame error figures (diff_min, diff_max,
+    diff_mean, diff_rms, rel_l2, psnr, nan_count: native.frame_summary) and the per-pixel error map over all frames
+    (pixel_diff_mean, pixel_diff_rms, pixel_diff_min, pixel_diff_max, pixel_nan_count in the frame's shape: native.pixel_summary).
+    Both tables stream through the GPU once, in chunks of config.report_chunk_rows frames (default: what fills one of hostio's
+    staging buffers, at least one frame -- a frame larger than a staging buffer grows the buffer); per chunk one bamd_frame_stats
+    and one bamd_pixel_moments call.  Under data parallelism each rank takes a contiguous slice of the frames: the per-frame rows
+    are gathered in rank order (never summed: a frame's values are the bits one rank computed), the pixel sums and counts are SUM-,
+    the pixel extrema MIN- / MAX-all-reduced.  config.report_diff = True (default False) also stores `diff`, every difference image.
+    Returns the dict that rank 0 also writes to output/plotting/frame_stats.npz."""
+    before, after = _frame_tables(config, output_path)
+    device = get_device()
+    rank, world = bdist.rank_world()
+    n, shape = before.shape[0], tuple(before.shape[1:])
+    elems = int(np.prod(shape))
+    t_dtype, h_dtype = hostio._device_dtype(np.result_type(before.dtype, after.dtype))
+    lo, hi = bdist.shard_rows(n, rank, world)
+    chunk = report_chunk_rows(config, 2 * elems * np.dtype(h_dtype).itemsize)
+    want_diff = bool(getattr(config, "report_diff", False))
+
+    raw = torch.empty((len(native.FRAME_ROWS), hi - lo), dtype=torch.float64, device=device)
+    empty = torch.empty((0, elems), dtype=t_dtype, device=device)
+    acc = native.pixel_moments_raw(empty, empty)               # the neutral elements (a rank may own no frames)
+    diff = torch.empty((hi - lo, elems), dtype=t_dtype, device=device) if want_diff else None
+    for a in range(lo, hi, chunk):
+        e = min(a + chunk, hi)
+        plan = hostio.RowPlan("range", n, lo=a, hi=e, count=e - a)
+        b_dev = hostio.upload_rows(before, plan, device).to(t_dtype).reshape(e - a, elems)
+        a_dev = hostio.upload_rows(after, plan, device).to(t_dtype).reshape(e - a, elems)      # (.to: a no-op unless the archives differ in dtype)
+        raw[:, a - lo:e - lo] = native.frame_stats(b_dev, a_dev, diff[a - lo:e - lo] if want_diff else None)
+        native.pixel_moments_raw(b_dev, a_dev, out=acc)
+    rows = raw.t().contiguous()                                # (n_local, 10): frames are rows, as gather_rows wants them
+    if world > 1:
+        import torch.distributed as td
+        rows = bdist.gather_rows(rows, n, dst=0)
+        for idx, op in ((native.PIXEL_SUM_ROWS, td.ReduceOp.SUM), (native.PIXEL_MIN_ROWS, td.ReduceOp.MIN),
+                        (native.PIXEL_MAX_ROWS, td.ReduceOp.MAX)):
+            part = acc[list(idx)].contiguous()
+            td.all_reduce(part, op=op)
+            acc[list(idx)] = part
+    diff_host = _gather_rows(diff, n, world) if want_diff else None
+    if rank != 0:
+        return None
+    per_frame = native.frame_summary(rows.t(), elems, h_dtype)
+    per_pixel = {k: v.reshape(shape) for k, v in native.pixel_summary(acc, n).items()}
+    sums = rows.cpu().numpy()
+    sumsq, before_sumsq = (float(np.cumsum(sums[:, k])[-1]) if n else 0.0 for k in (7, 8))      # in frame order
+    with np.errstate(all="ignore"):
+        totals = {"table_diff_rms": np.float64(np.sqrt(np.float64(sumsq) / np.float64(n * elems))),
+                  "table_rel_l2": np.float64(np.sqrt(np.float64(sumsq) / np.float64(before_sumsq)))}
+    result = {"shape": np.array((n,) + shape, dtype=np.int64)}
+    result.update(per_frame)
+    result.update(per_pixel)
+    result.update(totals)
+    if want_diff:
+        result["diff"] = diff_host.reshape((n,) + shape)
+    os.makedirs(os.path.join(output_path, "plotting"), exist_ok=True)
+    np.savez(os.path.join(output_path, "plotting", "frame_stats.npz"), **result)
+    print("=== Frame report ===")
+    print(f"{n} frames of {' x '.join(str(d) for d in shape)}: difference RMS {totals['table_diff_rms']:.6g}, relative L2 error "
+          f"{totals['table_rel_l2']:.6g}, {int(per_frame['nan_count'].sum())} NaN elements")
+    with np.errstate(invalid="ignore"):
+        worst = np.argsort(-np.nan_to_num(per_frame["diff_rms"], nan=np.inf), kind="stable")[:5]
+    for k in worst:
+        print(f"frame {int(k)}: difference RMS {per_frame['diff_rms'][k]:.6g} min {per_frame['diff_min'][k]:.6g} max "
+              f"{per_frame['diff_max'][k]:.6g}; colour scale {per_frame['vmin'][k]:.6g} .. {per_frame['vmax'][k]:.6g}; PSNR "
+              f"{per_frame['psnr'][k]:.4g} dB")
     return result

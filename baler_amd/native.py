@@ -50,6 +50,8 @@ SYMBOLS = (
     "bamd_allreduce_sum", "bamd_train_epoch_dp", "bamd_create_act", "bamd_act_of", "bamd_create_pjconv",
     "bamd_column_moments", "bamd_column_hist",
 )
+# the frame statistics of the 2-D report have a header of their own (include/baler_amd_frames.h)
+FRAME_SYMBOLS = ("bamd_frame_stats", "bamd_pixel_moments")
 PJ_FEATURES = 784      # PJ_Conv_AE: one 28 x 28 frame per row
 
 
@@ -120,7 +122,9 @@ def lib():
     L.bamd_apply_deltas.argtypes = [vp, ci, ci, vp, vp, vp, i64, vp]
     L.bamd_column_moments.argtypes = [vp, vp, ci, i64, ci, ci, dbl, vp, ci, vp]
     L.bamd_column_hist.argtypes = [vp, vp, ci, i64, ci, ci, dbl, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp]
-    for name in SYMBOLS:
+    L.bamd_frame_stats.argtypes = [vp, vp, ci, i64, i64, vp, vp, vp]
+    L.bamd_pixel_moments.argtypes = [vp, vp, ci, i64, i64, vp, ci, vp]
+    for name in SYMBOLS + FRAME_SYMBOLS:
         getattr(L, name)
     _lib = L
     return L
@@ -393,6 +397,106 @@ def column_hist(before, after, edges_resp=None, edges_resid=None, edges_val=None
                                       _ptr(ptr["val"]), cnt["val"], _ptr(res.get("before")), _ptr(res.get("after")),
                                       int(accumulate), _stream(before)), "bamd_column_hist")
     return res
+
+
+# ---- frame statistics: the report mode for 2-D data (include/baler_amd_frames.h) ---------------------------------------------------
+# rows of bamd_frame_stats' (10, n_frames) output and of bamd_pixel_moments' (5, frame_elems) output
+FRAME_ROWS = ("before_min", "before_max", "after_min", "after_max", "diff_min", "diff_max", "diff_sum", "diff_sumsq",
+              "before_sumsq", "nan_count")
+PIXEL_ROWS = ("diff_sum", "diff_sumsq", "diff_min", "diff_max", "nan_count")
+PIXEL_SUM_ROWS, PIXEL_MIN_ROWS, PIXEL_MAX_ROWS = (0, 1, 4), (2,), (3,)
+
+
+def _frame_pair(what, before, after):
+    """Two device tensors (n, ...) of one dtype and shape, at least 2-D -> their (n, F) views (the checks of _table_pair)."""
+    before, after = _dev_tensor(before), _dev_tensor(after)
+    if before.dtype != after.dtype or before.shape != after.shape or before.dim() < 2:
+        raise NativeError(f"{what}: before and after must be two (n, ...) tables of frames of one dtype and shape")
+    _same_device(what, before, after)
+    f = 1
+    for d in before.shape[1:]:
+        f *= int(d)
+    if f < 1:
+        raise NativeError(f"{what}: frames without elements")
+    return before.reshape(before.shape[0], f), after.reshape(after.shape[0], f)
+
+
+def frame_stats(before, after, diff=None):
+    """bamd_frame_stats: -> the (10, n) float64 device tensor of per-frame extrema and sums (rows: FRAME_ROWS) of two device tensors
+    (n, ...), d = before - after.  ``diff``: a tensor like ``before`` that receives d bit for bit.  A frame's ten values do not
+    depend on n, on its index or on how the table was cut into calls."""
+    before, after = _frame_pair("frame_stats", before, after)
+    n, f = before.shape
+    if diff is not None:
+        diff = _dev_tensor(diff)
+        if diff.dtype != before.dtype or diff.numel() != before.numel() or (n and diff.shape[0] != n):
+            raise NativeError("frame_stats: diff must be a tensor of before's dtype and shape")
+        _same_device("frame_stats", before, diff)
+    out = torch.empty((len(FRAME_ROWS), n), dtype=torch.float64, device=before.device)
+    if n == 0:
+        return out
+    with torch.cuda.device(before.device):
+        _check(lib().bamd_frame_stats(_ptr(before), _ptr(after), _dt(before), n, f, _ptr(out), _ptr(diff), _stream(before)),
+               "bamd_frame_stats")
+    return out
+
+
+def frame_summary(raw, frame_elems, dtype=None):
+    """The (10, n) rows of bamd_frame_stats (tensor or array) of frames of ``frame_elems`` = F elements -> dict of numpy arrays of
+    length n.  vmin / vmax: the colour scale of plotting.plot_2D's three panels (plotting.py:417-418), min / max over both tiles,
+    NaN where the frame holds a NaN (np.amin / np.amax propagate it), cast to the table's ``dtype`` (numpy dtype; default float64);
+    diff_min, diff_max, diff_mean = sum / F and diff_rms = sqrt(sum of squares / F) of d = before - after; rel_l2 = sqrt(sum d^2 /
+    sum before^2); psnr = 20 log10((max - min of before) / diff_rms); nan_count (int64).  Zero denominators give inf / NaN."""
+    import numpy as np
+    r = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    d = dict(zip(FRAME_ROWS, np.asarray(r, dtype=np.float64)))
+    f = float(frame_elems)
+    dt = np.dtype(np.float64 if dtype is None else dtype)
+    has_nan = d["nan_count"] != 0
+    with np.errstate(all="ignore"):
+        rms = np.sqrt(d["diff_sumsq"] / f)
+        out = {"vmin": np.where(has_nan, np.nan, np.minimum(d["before_min"], d["after_min"])).astype(dt),
+               "vmax": np.where(has_nan, np.nan, np.maximum(d["before_max"], d["after_max"])).astype(dt),
+               "diff_min": d["diff_min"], "diff_max": d["diff_max"],
+               "diff_mean": d["diff_sum"] / f, "diff_rms": rms,
+               "rel_l2": np.sqrt(d["diff_sumsq"] / d["before_sumsq"]),
+               "psnr": 20.0 * np.log10((d["before_max"] - d["before_min"]) / rms),
+               "nan_count": d["nan_count"].astype(np.int64)}
+    return out
+
+
+def pixel_moments_raw(before, after, out=None):
+    """bamd_pixel_moments: -> the (5, F) float64 device tensor of per-pixel sums, extrema and NaN counts over the frames (rows:
+    PIXEL_ROWS) of two device tensors (n, ...), d = before - after.  With ``out`` (the result of an earlier call) this call's frames
+    are ADDED to it: a table can be fed in frame chunks."""
+    before, after = _frame_pair("pixel_moments", before, after)
+    n, f = before.shape
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty((len(PIXEL_ROWS), f), dtype=torch.float64, device=before.device)
+    elif tuple(out.shape) != (len(PIXEL_ROWS), f) or out.dtype != torch.float64:
+        raise NativeError("pixel_moments: out must be a (5, frame_elems) float64 tensor")
+    _same_device("pixel_moments", before, _dev_tensor(out))
+    with torch.cuda.device(before.device):
+        _check(lib().bamd_pixel_moments(_ptr(before), _ptr(after), _dt(before), n, f, _ptr(out), int(accumulate), _stream(before)),
+               "bamd_pixel_moments")
+    return out
+
+
+def pixel_summary(raw, n_frames):
+    """The (5, F) rows of bamd_pixel_moments over ``n_frames`` frames (tensor or array) -> dict of numpy arrays of length F:
+    pixel_diff_mean = sum / m and pixel_diff_rms = sqrt(sum of squares / m) with m = n_frames - nan_count (a pixel that is NaN in
+    every frame: NaN), pixel_diff_min, pixel_diff_max, pixel_nan_count (int64).  A NaN among a pixel's values makes its sums NaN, as
+    in numpy; the count says how many frames are behind it."""
+    import numpy as np
+    r = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    d = dict(zip(PIXEL_ROWS, np.asarray(r, dtype=np.float64)))
+    m = float(n_frames) - d["nan_count"]
+    with np.errstate(all="ignore"):
+        m = np.where(m > 0, m, np.nan)
+        return {"pixel_diff_mean": d["diff_sum"] / m, "pixel_diff_rms": np.sqrt(d["diff_sumsq"] / m),
+                "pixel_diff_min": d["diff_min"], "pixel_diff_max": d["diff_max"],
+                "pixel_nan_count": d["nan_count"].astype(np.int64)}
 
 
 # ---- model handle ---------------------------------------------------------------------------------

@@ -517,4 +517,8 @@ int bamd_column_hist(const void *before, const void *after, int dtype, int64_t n
 #ifdef __cplusplus
 }
 #endif
+
+/* The report mode for 2-D data -- per-frame and per-pixel statistics of two tables of frames -- has a header of its own. */
+#include "baler_amd_frames.h"
+
 #endif /* BALER_AMD_H */
